@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json metric on synthetic data: prefill+decode tokens/s @ 32K context, 50% KV retention
-(Compactor scoring + eviction overlapped with prefill), one MI355X per rank; plus the decode-attention kernel's
-achieved HBM GB/s against the roofline and a CPU baseline of the same hot path (oracle, host cores).
+(Compactor scoring + eviction overlapped with prefill), one MI355X per rank.  A plain run sets up, warms up, times the
+steps and prints the tokens/s line; with --full it also measures the decode-attention kernel's achieved HBM GB/s against
+the roofline, the prefill-attention and store-stream kernels, a 4-sequences-per-GPU leg and a CPU baseline of the same
+hot path (oracle, host cores), and adds them to the line.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload C3|C2|C4|tiny] [--ctx L --new T --ratio r]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                    [--workload C3|C2|C4|tiny] [--ctx L --new T --ratio r]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+--dump-outputs DIR writes what the last timed step returned to its caller - the generated token ids of every sequence -
+as DIR/tokens.npy (float64 [sequences, new]; DIR/tokens_rank<r>.npy per rank in a multi-GPU run).  Prompts and weights
+are seeded, so the same arguments give the same inputs in every run.
 
 A "step" = one generate call (reference LLM.generate -> scheduler throughput, scheduler.py:203-205):
 prefill of one `ctx`-token prompt per rank with scoring/selection/compaction on the store stream, then `new`
@@ -509,6 +516,12 @@ def main():
     ap.add_argument("--ratio", type=float, default=-1.0)
     ap.add_argument("--method", default="", choices=["", "COMPACTOR", "SNAPKV", "NONE"], help="override the workload's")
     ap.add_argument("--seqs", type=int, default=1, help="sequences per GPU (the metric's configs use 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline legs, the 4-sequences-per-GPU leg and the CPU baseline "
+                         "(several minutes); the --no-roofline / --no-multi-seq / --no-cpu-baseline / --no-live-pmc switches "
+                         "take single legs out of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the token ids the last timed step returned as DIR/tokens.npy")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-multi-seq", action="store_true", help="skip the extra 4-sequences-per-GPU leg (N=1 only)")
@@ -568,10 +581,10 @@ def main():
     method = CompressionMethod[method_name]
     cfg = {"llama": bs.LLAMA31_8B, "qwen3": bs.QWEN3_8B, "tiny": bs.TINY}[shape]
     nseq = max(1, args.seqs) if args.workload != "C5" or args.seqs > 1 else 8
-    # N = 1 only: an extra, untimed-for-`value` leg repeats the workload with MULTI sequences per GPU (what a serving
-    # batch looks like); the KV pool is sized for it up front, which does not change the 1-sequence timings
+    # --full, N = 1 only: an extra, untimed-for-`value` leg repeats the workload with MULTI sequences per GPU (what a
+    # serving batch looks like); the KV pool is sized for it up front, which does not change the 1-sequence timings
     MULTI = 4
-    multi_leg = world == 1 and nseq == 1 and not args.no_multi_seq and args.workload != "tiny"
+    multi_leg = args.full and world == 1 and nseq == 1 and not args.no_multi_seq and args.workload != "tiny"
     max_seqs = MULTI if multi_leg else nseq
     model = bs.ModelShell(cfg, dev, max_model_len=ctx + new, seed=0)
     # The product's engine drives the shell model: scheduler, paged KV cache (pages for the FULL uncompressed length
@@ -635,10 +648,17 @@ def main():
 
     fence()
     t0 = time.perf_counter()
+    last_out = None
     for _ in range(args.steps):
-        step()
+        last_out = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and last_out is not None:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "tokens.npy" if world == 1 else f"tokens_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), np.asarray(last_out, dtype=np.float64))
     if dist is not None:
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -672,7 +692,7 @@ def main():
             "decode_merge_fallback": bool(merge_fallbacks),
         },
     }
-    if rank == 0 and args.no_roofline:
+    if rank == 0 and (args.no_roofline or not args.full):
         print(json.dumps(result), flush=True)
     elif rank == 0:
         state = prefill_only(llm, prompts, bcp, ratio)  # a prefill whose cache stays allocated: the real cache

@@ -7,7 +7,7 @@ R=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$R
 mkdir -p "$O"
-B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-multi-seq --no-live-pmc"
+B="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-multi-seq --no-live-pmc"
 # 1. kernel trace + the tool's own stats of the bench command (C3 through the engine); the decode kernels' mean durations
 #    of THIS trace become profiles/<R>_bench_decode_rocprof.json, which bench.py prints beside its event-timed figure
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- $B > "$O/bench_under_rocprof.log" 2>&1
@@ -105,14 +105,14 @@ timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d "$O/ktab_overl
 rm -rf "$O/ktab_serial" "$O/ktab_overlap"
 echo "[7/8] A/B done"
 # 8. the bench lines: default run (C3, with cpu_baseline), C2, C4; optional (COLLECT_C5=1, ~3 min): one GPU's share of C5
-python3 bench.py > "$O/bench_c3.log" 2>&1
+python3 bench.py --full > "$O/bench_c3.log" 2>&1
 grep "^{\"metric\"" "$O/bench_c3.log" | tail -1 > "$O/${R}_bench_c3.json"
-python3 bench.py --workload C2 --steps 2 --warmup 1 --no-cpu-baseline > "$O/bench_c2.log" 2>&1
+python3 bench.py --full --workload C2 --steps 2 --warmup 1 --no-cpu-baseline > "$O/bench_c2.log" 2>&1
 grep "^{\"metric\"" "$O/bench_c2.log" | tail -1 > "$O/${R}_bench_c2.json"
-python3 bench.py --workload C4 --steps 2 --warmup 1 --no-cpu-baseline > "$O/bench_c4.log" 2>&1
+python3 bench.py --full --workload C4 --steps 2 --warmup 1 --no-cpu-baseline > "$O/bench_c4.log" 2>&1
 grep "^{\"metric\"" "$O/bench_c4.log" | tail -1 > "$O/${R}_bench_c4.json"
 if [ "${COLLECT_C5:-0}" = "1" ]; then
-  python3 bench.py --workload C5 --steps 1 --warmup 0 --no-cpu-baseline > "$O/bench_c5.log" 2>&1
+  python3 bench.py --full --workload C5 --steps 1 --warmup 0 --no-cpu-baseline > "$O/bench_c5.log" 2>&1
   grep "^{\"metric\"" "$O/bench_c5.log" | tail -1 > "$O/${R}_bench_c5_per_gpu.json"
 fi
 echo "[8/8] bench lines done"
