@@ -54,6 +54,13 @@ SIGNATURES = {
                                      _I, _I, _I, _I, _I, _P]),
     "cvllm_qkv_rope_producer": (_I, [_P, _L, _P, _P, _P, _P, _F, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
                                      _I, _I, _I, _I, _I, _P]),
+    # FP8 cache: the siblings' argument lists + (k_scale, v_scale)
+    "cvllm_store_decode_kv_fp8": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "cvllm_store_all_kv_fp8": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P,
+                                    _P]),
+    "cvllm_compact_store_fp8": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
+                                     _I, _I, _P, _P, _P]),
+    "cvllm_decode_attn_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "cvllm_rank_workspace_bytes": (_Z, [_I, _I, _I]),
     "cvllm_rank_indices": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
 }
@@ -107,6 +114,18 @@ def dtype_code(dt: torch.dtype) -> int:
     if dt == torch.bfloat16:
         return 1
     raise TypeError(f"compactor_vllm_amd kernels support float16 / bfloat16, got {dt}")
+
+
+FP8 = torch.float8_e4m3fn  # element type of an FP8 KV cache (OCP e4m3 codes + one fp32 scale per row)
+
+
+def check_fp8_scales(k_cache: torch.Tensor, k_scale, v_scale) -> None:
+    """The scale arrays that go with an FP8 cache: present, fp32, contiguous, one entry per cache row."""
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        assert s is not None, f"an FP8 cache needs {name}"
+        assert s.dtype == torch.float32 and s.is_contiguous(), f"{name} must be contiguous float32"
+        assert s.shape == (k_cache.shape[0],), f"{name} must hold one scale per cache row"
+    require_cuda(k_scale, v_scale)
 
 
 def score_dtype_code(dt: torch.dtype) -> int:

@@ -108,6 +108,8 @@ def head_sparse_decode_attention(
     key_split: int = None,
     *,
     return_lse: bool = False,
+    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    v_scale: torch.Tensor | None = None,
 ):
     """Same contract as the reference wrapper (sparse_decode_kernel.py:10-68).  `return_lse=True` (extension, used by
     attention/cross_gpu_decode.py) also returns lse [B, HQ] fp32: the natural-log LSE of the scaled logits.
@@ -152,6 +154,18 @@ def head_sparse_decode_attention(
     if n_splits > 1:
         ws_bytes = L.cvllm_decode_workspace_bytes(B, HQ, D, n_splits)
         ws = _workspace(q.device, ws_bytes)
+    if k.dtype == _lib.FP8:  # e4m3 codes + per-row scales: the MFMA stage-1 kernel of csrc/kv_fp8.hip
+        assert v.dtype == _lib.FP8
+        _lib.check_fp8_scales(k, k_scale, v_scale)
+        if return_lse:
+            raise NotImplementedError("the LSE output (split-KV shards) is not offered on an FP8 cache")
+        st = L.cvllm_decode_attn_fp8(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), out.data_ptr(),
+            seq_lens_bh.data_ptr(), page_table.data_ptr(), batch_mapping.data_ptr(), _lib.ptr(ws), ws_bytes, B, HQ,
+            HKV, D, PAGE_SIZE, n_lp, float(sm_scale), n_splits, _lib.dtype_code(q.dtype), _lib.stream(),
+        )
+        _lib.check(st, "cvllm_decode_attn_fp8")
+        return out
     if return_lse:
         lse = torch.empty((B, HQ), dtype=torch.float32, device=q.device)
         st = L.cvllm_decode_attn_lse(
@@ -189,6 +203,8 @@ def fused_decode_step(
     """decode_store_kv + head_sparse_decode_attention + length write-back of the reference's decode branch
     (layers/attention.py:127-160) in one C-ABI call that works directly on the layer's length table."""
     _lib.require_cuda(q, key, value, k_cache, v_cache, bh_seq_lens_layer, page_table, batch_mapping)
+    if k_cache.dtype == _lib.FP8:
+        raise NotImplementedError("no fused append on an FP8 cache: decode_store_kv, then head_sparse_decode_attention")
     B, HQ, D = q.shape
     assert key.shape == (B, HKV, D) and value.shape == (B, HKV, D)
     if not q.is_contiguous():

@@ -114,6 +114,8 @@ def extract_and_store_top_kv(
     PAD_TO_PAGE_SIZE: bool = True,
     K_TILE: int = 16,
     padding: float = -float("inf"),
+    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    v_scale: torch.Tensor | None = None,
 ):
     """scores -> retained (token, head) pairs -> paged cache, on the current stream (reference
     common.py:126-168).  `top_k` (the reference passes max_len*H, i.e. "rank everything") and
@@ -131,13 +133,17 @@ def extract_and_store_top_kv(
     bm = _lib.i32(batch_mapping)
     sk_n, sk_h, _ = new_keys.stride()
     sv_n, sv_h, _ = new_vals.stride()
-    st = _lib.lib().cvllm_compact_store(
-        new_keys.data_ptr(), new_vals.data_ptr(), sk_n, sk_h, sv_n, sv_h, kept.data_ptr(), new_lens.data_ptr(),
-        cu.data_ptr(), bh_lens.data_ptr(), page_table.data_ptr(), bm.data_ptr(), k_cache.data_ptr(),
-        v_cache.data_ptr(), B, H, D, int(kept.shape[-1]), int(PAGE_SIZE), page_table.shape[-1],
-        _lib.dtype_code(new_keys.dtype), _lib.stream(),
-    )
-    _lib.check(st, "cvllm_compact_store")
+    args = (new_keys.data_ptr(), new_vals.data_ptr(), sk_n, sk_h, sv_n, sv_h, kept.data_ptr(), new_lens.data_ptr(),
+            cu.data_ptr(), bh_lens.data_ptr(), page_table.data_ptr(), bm.data_ptr(), k_cache.data_ptr(),
+            v_cache.data_ptr(), B, H, D, int(kept.shape[-1]), int(PAGE_SIZE), page_table.shape[-1],
+            _lib.dtype_code(new_keys.dtype), _lib.stream())
+    if k_cache.dtype == _lib.FP8:  # quantising compaction: a kept row's scale moves with its codes
+        _lib.check_fp8_scales(k_cache, k_scale, v_scale)
+        st = _lib.lib().cvllm_compact_store_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr())
+        _lib.check(st, "cvllm_compact_store_fp8")
+    else:
+        st = _lib.lib().cvllm_compact_store(*args)
+        _lib.check(st, "cvllm_compact_store")
     bh_lens.copy_(new_lens)  # lengths become visible after the rows are enqueued (same stream)
     return kept, new_lens
 
@@ -156,6 +162,8 @@ def compact_cache_inplace(
     """Move the kept rows of every (b, h) down inside the paged cache (last chunk of a chunked prefill): the same final
     cache as `extract_and_store_top_kv` fed with the whole sequence's packed keys / values."""
     _lib.require_cuda(kept_idx, new_lens, dst_base, src_base, page_table, batch_mapping, k_cache, v_cache)
+    if k_cache.dtype == _lib.FP8:
+        raise NotImplementedError("in-place compaction has no FP8 form (chunked prefill is off with an FP8 cache)")
     B, H, max_len = kept_idx.shape
     st = _lib.lib().cvllm_compact_cache_inplace(
         kept_idx.data_ptr(), new_lens.data_ptr(), _lib.i32(dst_base).data_ptr(), _lib.i32(src_base).data_ptr(),

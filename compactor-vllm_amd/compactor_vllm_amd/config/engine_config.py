@@ -32,8 +32,11 @@ class LLMConfig:
     leverage_sketch_size: int = 48
     attention_backend: AttentionBackend = AttentionBackend.COMPACTOR_TRITON
     show_progress_bar: bool = True
+    kv_cache_dtype: str = "auto"  # "auto" = the model dtype; "fp8_e4m3" = e4m3 codes + one fp32 scale per cache row
 
     def __post_init__(self):
+        if self.kv_cache_dtype not in ("auto", "fp8_e4m3"):
+            raise ValueError(f"kv_cache_dtype must be 'auto' or 'fp8_e4m3', got {self.kv_cache_dtype!r}")
         if self.path is not None and not os.path.isdir(self.path):
             raise NotADirectoryError(f"Engine config dir {self.path} does not exist")
         if self.tensor_parallel_size <= 0 or self.tensor_parallel_size > 8:

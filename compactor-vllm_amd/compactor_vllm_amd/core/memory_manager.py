@@ -46,9 +46,15 @@ class KVCacheManager:
         self.max_batched_tokens = max_batched_tokens
         self.seq_id_to_batch: dict = {}
         self.chunked_prefill = True  # prompts longer than max_batched_tokens are prefilled in chunks (scheduler.py)
+        self.fp8 = getattr(config, "kv_cache_dtype", "auto") == "fp8_e4m3"
+        self.cache_dtype = torch.float8_e4m3fn if self.fp8 else self.model_dtype
+        if self.fp8:
+            self.chunked_prefill = False  # the prefill kernel cannot read an FP8 prefix
 
     # ---- sizing ------------------------------------------------------------------------------------------------
     def bytes_per_page_all_layers(self) -> int:
+        if self.fp8:  # one byte per element + one fp32 scale per row
+            return self.num_layers * 2 * self.page_size * (self.head_dim + 4)
         elt = torch.empty((), dtype=self.model_dtype).element_size()
         return self.num_layers * 2 * self.page_size * self.head_dim * elt
 
@@ -69,11 +75,12 @@ class KVCacheManager:
         self.paged_cache = PagedKVCache(
             num_layers=self.num_layers, H_kv=self.num_kv_heads, head_dim=self.head_dim, page_size=self.page_size,
             num_pages=int(self.num_pages), max_num_batches=self.max_num_batches, device=self.device,
-            dtype=self.model_dtype, max_logical_pages_per_head=int(self.max_pages_per_batch))
+            dtype=self.cache_dtype, max_logical_pages_per_head=int(self.max_pages_per_batch))
         if self.max_batched_tokens is None:
             self.max_batched_tokens = self.estimate_max_batched_tokens()
         for layer_index, attn in enumerate(attention_modules(model)):
             attn.k_cache, attn.v_cache, attn.page_table, attn.bh_seq_lens = self.paged_cache.layer_slices(layer_index)
+            attn.k_scale, attn.v_scale = self.paged_cache.layer_scale_slices(layer_index)
             attn.page_size = self.page_size
 
     def estimate_max_batched_tokens(self) -> int:

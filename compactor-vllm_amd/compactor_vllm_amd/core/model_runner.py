@@ -156,6 +156,9 @@ class ModelRunner:
         from ..compression.compression_config import SequenceCompressionParams
         from ..config.sampling_params import SamplingParams
 
+        if self.kv_manager.fp8:
+            raise NotImplementedError("prefix reuse needs prefill attention over cached rows, which cannot read an FP8 "
+                                      "cache (kv_cache_dtype='fp8_e4m3')")
         params = batch_compression_params if batch_compression_params is not None else BatchCompressionParams()
         method, chunk = self._scoring_key(params)
         P = (len(token_ids) // PREFIX_ALIGN) * PREFIX_ALIGN

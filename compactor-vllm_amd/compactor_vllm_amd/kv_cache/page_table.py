@@ -91,6 +91,10 @@ class PagedKVCache(torch.nn.Module):
         self.max_pages_per_head = max_logical_pages_per_head
         self.max_num_batches = rows
         self.kv_cache = torch.empty((2, num_layers, num_pages * self.page_size, head_dim), dtype=dtype, device=device)
+        # FP8 cache: e4m3 codes above + one fp32 scale per physical row, K = 0 / V = 1 (same row index as the codes)
+        self.kv_scale: Optional[torch.Tensor] = None
+        if dtype == torch.float8_e4m3fn:
+            self.kv_scale = torch.empty((2, num_layers, num_pages * self.page_size), dtype=torch.float32, device=device)
         per_head = dict(device=device, dtype=torch.int32)
         self.page_table = torch.zeros((num_layers, rows, self.H_kv, max_logical_pages_per_head), **per_head)
         self.bh_seq_lens = torch.zeros((num_layers, rows, self.H_kv), **per_head)
@@ -153,10 +157,18 @@ class PagedKVCache(torch.nn.Module):
             pool.give_back(batch_index, pages)
             released += len(pages)
         self.bh_num_pages[:, batch_index] = keep
-        return released * self.page_size * self.head_dim * self.kv_cache.element_size() * 2
+        row_bytes = self.head_dim * self.kv_cache.element_size() + (4 if self.kv_scale is not None else 0)
+        return released * self.page_size * row_bytes * 2
 
     # ---- views --------------------------------------------------------------------------------------------------
     def layer_slices(self, layer: int):
         """(k_cache, v_cache, page_table, bh_seq_lens) of one layer: what an `Attention` module holds (:293-313)."""
         assert 0 <= layer < self.num_layers
         return self.kv_cache[0, layer], self.kv_cache[1, layer], self.page_table[layer], self.bh_seq_lens[layer]
+
+    def layer_scale_slices(self, layer: int):
+        """(k_scale, v_scale) of one layer of an FP8 cache, (None, None) otherwise."""
+        assert 0 <= layer < self.num_layers
+        if self.kv_scale is None:
+            return None, None
+        return self.kv_scale[0, layer], self.kv_scale[1, layer]

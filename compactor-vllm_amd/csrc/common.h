@@ -106,6 +106,13 @@ int store_decode_kv_impl(const void* key, const void* value, int64_t sk_b, int64
                          void* v_cache, int B, int HKV, int D, int page_size, int n_logical_pages_max,
                          int reserved_batch, int dtype, int lens_by_row, cvllm_stream_t stream);
 
+// decode_attn.hip: the split-merge workspace starts with a header (word 0 = in-launch merge error flag, the rest reserved
+// and zero); behind it the two-kernel path keeps part_o[B,S,HQ,D] then part_lse[B,S,HQ] (fp32).  launch_decode_stage2
+// merges them into out[B,HQ,D] and hands the words it read back zeroed (kv_fp8.hip's stage 1 uses it too).
+constexpr size_t DEC_WS_HEADER = 256;
+int launch_decode_stage2(float* part_o, float* part_lse, void* out, int B, int HQ, int D, int S, int dtype,
+                         hipStream_t stream);
+
 // dynamic-LDS limit of a kernel, set once per (kernel instantiation, device): the attribute lives on the device's
 // code object, so a second device in the same process needs its own call
 template <typename K>

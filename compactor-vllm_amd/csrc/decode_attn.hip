@@ -1038,7 +1038,24 @@ __global__ __launch_bounds__(256) void decode_merge_shards_kernel(const uint16_t
   *reinterpret_cast<uint4*>(out + (size_t)row * D + 8 * c) = o;
 }
 
-constexpr size_t DEC_WS_HEADER = 256;  // bytes: word 0 = in-launch merge error flag; the rest reserved (zero)
+// stage 2 on its own (no fused append, no LSE output): the merge of kv_fp8.hip's stage-1 partials
+int launch_decode_stage2(float* part_o, float* part_lse, void* out, int B, int HQ, int D, int S, int dtype,
+                         hipStream_t stream) {
+  if (D != 64 && D != 128) return CVLLM_ERR_SHAPE;
+  const dim3 grid(B * HQ), block(256);
+#define CVLLM_STAGE2(T_, D_)                                                                                          \
+  hipLaunchKernelGGL((decode_stage2_kernel<T_, D_>), grid, block, 0, stream, part_o, part_lse, (uint16_t*)out, HQ, S, \
+                     (int*)nullptr, (const int*)nullptr, 1, 0, 0, -1, (float*)nullptr)
+  if (dtype == CVLLM_F16) {
+    if (D == 64) CVLLM_STAGE2(F16, 64); else CVLLM_STAGE2(F16, 128);
+  } else if (dtype == CVLLM_BF16) {
+    if (D == 64) CVLLM_STAGE2(BF16, 64); else CVLLM_STAGE2(BF16, 128);
+  } else {
+    return CVLLM_ERR_SHAPE;
+  }
+#undef CVLLM_STAGE2
+  return check_launch();
+}
 
 struct DecodeArgs {
   const void *q, *key_new, *val_new;

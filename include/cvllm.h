@@ -289,6 +289,45 @@ int cvllm_qkv_rope_producer(const void* qkv, int64_t s_n, const int64_t* positio
                             int n_logical_pages_max, int N, int HQ, int HKV, int D, int max_pos, int dtype,
                             cvllm_stream_t stream);
 
+/* ---- FP8 (OCP e4m3) paged KV cache ---------------------------------------------------------------------------
+ * Codes: k_cache / v_cache [cache_rows, D], ONE byte per element (float8_e4m3fn); a page is page_size * D bytes, the
+ * paging is unchanged.  Scales: k_scale / v_scale [cache_rows] fp32, one per physical cache row, indexed like the codes
+ * (the scales of a page are page_size * 4 contiguous bytes).  Quantisation is dynamic and per row, for a row x[D]:
+ *     a = max(max_d |float(x_d)|, 1e-30f);  scale = a / 448;  inv = 448 / a   (both IEEE round-to-nearest divisions)
+ *     code_d = e4m3(float(x_d) * inv)   (round to nearest even; |x * inv| <= 448, never saturates)
+ * and the value read back is float(code) * scale in fp32.  NaN / Inf inputs are unspecified.
+ *
+ * The three stores take the argument list of their 16-bit siblings (cvllm_store_decode_kv, cvllm_store_all_kv,
+ * cvllm_compact_store; `dtype` = the SOURCE element type, strides multiples of 8 elements) plus the two scale arrays;
+ * row addressing, slot order, the reserved-row rule and the length updates are the siblings'.  D in {64, 128}.
+ * No workspace; capture safe where the sibling is.                                                              */
+int cvllm_store_decode_kv_fp8(const void* key, const void* value, int64_t sk_b, int64_t sk_h, int64_t sv_b,
+                              int64_t sv_h, const int32_t* batch_mapping, int32_t* bh_lens,
+                              const int32_t* page_table, void* k_cache, void* v_cache, int B, int HKV, int D,
+                              int page_size, int n_logical_pages_max, int reserved_batch, int dtype,
+                              cvllm_stream_t stream, float* k_scale, float* v_scale);
+int cvllm_store_all_kv_fp8(const void* new_keys, const void* new_values, int64_t sk_n, int64_t sk_h, int64_t sv_n,
+                           int64_t sv_h, const int32_t* cu_seqlens_k, const int32_t* batch_mapping,
+                           int32_t* bh_lens, const int32_t* page_table, void* k_cache, void* v_cache, int B,
+                           int total_tokens, int HKV, int D, int page_size, int n_logical_pages_max, int dtype,
+                           cvllm_stream_t stream, float* k_scale, float* v_scale);
+int cvllm_compact_store_fp8(const void* new_keys, const void* new_vals, int64_t sk_n, int64_t sk_h, int64_t sv_n,
+                            int64_t sv_h, const int32_t* kept_idx, const int32_t* new_lens,
+                            const int32_t* cu_seqlens_k, const int32_t* bh_lens0, const int32_t* page_table,
+                            const int32_t* batch_mapping, void* k_cache, void* v_cache, int B, int H, int D,
+                            int max_seqlen, int page_size, int n_logical_pages_max, int dtype,
+                            cvllm_stream_t stream, float* k_scale, float* v_scale);
+/* Decode attention over an FP8 cache: q / out [B,HQ,D] in `dtype` (f16 or bf16); lengths, page table, batch mapping,
+ * n_splits and the workspace as cvllm_decode_attn (cvllm_decode_workspace_bytes; zero when handed over, zero again
+ * afterwards).  D in {64, 128}, G in {1, 2, 4, 8}, page_size % 32 == 0, any n_logical_pages_max.  Splits are always
+ * merged by the second kernel (fp32 partials + LSE); rows with L == 0 produce zeros.  The grid depends on the integer
+ * arguments only: capture safe.  No fused append and no LSE output.                                             */
+int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
+                          const float* v_scale, void* out, const int32_t* seq_lens_bh, const int32_t* page_table,
+                          const int32_t* batch_mapping, void* workspace, size_t workspace_bytes, int B, int HQ,
+                          int HKV, int D, int page_size, int n_logical_pages_max, float sm_scale, int n_splits,
+                          int dtype, cvllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

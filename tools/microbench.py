@@ -54,6 +54,14 @@ def bench_decode(args):
     q = torch.randn(B, HQ, D, device=dev, dtype=dtype)
     splits_list = [args.splits] if args.splits else [16, 32, 64]
     bytes_alg = 2 * D * 2 * B * HKV * L + 2 * B * HQ * D * 2
+    fp8 = args.kv_dtype == "fp8"
+    if fp8:  # e4m3 codes + one fp32 scale per row (csrc/kv_fp8.hip); bytes = (2 D + 8) * sum L + 4 * B * HQ * D
+        caches = [(kc.to(torch.float8_e4m3fn), vc.to(torch.float8_e4m3fn)) for kc, vc in caches]
+        scales = [(torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005, torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005)
+                  for kc, _ in caches]
+        bytes_alg = (2 * D + 8) * B * HKV * L + 4 * B * HQ * D
+    else:
+        scales = [(None, None)] * len(caches)
     from compactor_vllm_amd import _lib
     if args.flush:
         junk_a = torch.empty(128 << 20, dtype=torch.uint8, device=dev)
@@ -62,16 +70,17 @@ def bench_decode(args):
         for S in splits_list:
             dk.plan_internal_splits = lambda n_bh, bound, ks, S=S: S
             # one HIP graph with `layers` launches over distinct caches: no host launch overhead in the timing
-            dk.head_sparse_decode_attention(q, caches[0][0], caches[0][1], lens, pt, bm, HKV, PS)
+            dk.head_sparse_decode_attention(q, caches[0][0], caches[0][1], lens, pt, bm, HKV, PS, k_scale=scales[0][0],
+                                            v_scale=scales[0][1])
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                for kc, vc in caches:
+                for (kc, vc), (ksc, vsc) in zip(caches, scales):
                     if args.flush:  # stream 256 MB through the L2s between launches: the metadata lines go cold, as they
                         junk_b.copy_(junk_a)  # do between two layers of a decode step (the GEMVs' weights in between)
-                    out = dk.head_sparse_decode_attention(q, kc, vc, lens, pt, bm, HKV, PS)
+                    out = dk.head_sparse_decode_attention(q, kc, vc, lens, pt, bm, HKV, PS, k_scale=ksc, v_scale=vsc)
             us = time_fn(g.replay, iters=50, warmup=max(3, int(40e3 / (25.0 * layers)))) / layers  # ~40 ms of warm replays: settled clocks
-            print(f"decode variant={variant} B={B} L={L} splits={S:3d} layers={layers}: {us:8.2f} us/(stage1+merge)  "
+            print(f"decode{' kv=fp8' if fp8 else ''} variant={variant} B={B} L={L} splits={S:3d} layers={layers}: {us:8.2f} us/(stage1+merge)  "
                   f"{bytes_alg / us / 1e6:7.3f} TB/s algorithmic", flush=True)
 
 
@@ -176,6 +185,8 @@ if __name__ == "__main__":
     ap.add_argument("--splits", type=int, default=0)
     ap.add_argument("--variant", type=int, default=-1)
     ap.add_argument("--fused-v", type=int, default=0, help="prefill: 1 = V (2 = K and V) as strided views of a fused qkv buffer")
+    ap.add_argument("--kv-dtype", choices=["model", "fp8"], default="model",
+                    help="decode: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
     ap.add_argument("--flush", action="store_true", help="decode: a 128 MB device copy between launches (cold metadata, as inside a decode step)")
     ap.add_argument("--iters", type=int, default=0)      # scoring: timed calls per item (0 = default)
     ap.add_argument("--warmup", type=int, default=-1)    # scoring: warm calls per item (-1 = default)
