@@ -2,7 +2,7 @@
 
 Mirror of the reference module `compactor_vllm/attention/sparse_varlen_kernel.py`
 (wrapper :11-197): same name, argument order and assertions; the Triton kernel (:277-519) is
-replaced by `cvllm_prefill_attn`.
+replaced by `cvllm_prefill_attn` (`cvllm_prefill_attn_fp8` over an FP8 cache).
 """
 from __future__ import annotations
 
@@ -28,13 +28,17 @@ def causal_sparse_varlen_with_cache(
     HKV: int,
     PAGE_SIZE: int,
     sm_scale=None,
+    k_scale=None,
+    v_scale=None,
 ):
     """out = softmax_causal(q [K_prefix || k]^T * scale) [V_prefix || v] per sequence and kv-head.
 
     q [N, HQ, D]; k, v [N, HKV, D] (last dim contiguous, arbitrary token stride — the model passes
     strided views of the fused qkv buffer); k_cache / v_cache [CACHE_SIZE, D]; seq_lens_bh [B, HKV] =
     cached prefix lengths BEFORE this step (per kv-head); global_page_table [MAX_BATCHES, HKV, P];
-    batch_mapping [B]; cu_seqlens_q [B+1].  `max_seqlen_k_cache` only keys the reference's autotuner
+    batch_mapping [B]; cu_seqlens_q [B+1].  With an FP8 cache (k_cache.dtype float8_e4m3fn: e4m3 codes) `k_scale` /
+    `v_scale` [CACHE_SIZE] fp32 are the rows' scales and the kernel is `cvllm_prefill_attn_fp8`: a cached element is read
+    back as (fp32(code) * scale) rounded to q.dtype.  `max_seqlen_k_cache` only keys the reference's autotuner
     (quirk Q10) and is ignored.  Returns [N, HQ, D] contiguous in q.dtype.
     """
     assert q.ndim == 3, "q should be [N, HQ, D]"
@@ -60,11 +64,16 @@ def causal_sparse_varlen_with_cache(
     bm = _lib.i32(batch_mapping)
     pt = _lib.i32(global_page_table)
     out = torch.empty((N, HQ, D), dtype=q.dtype, device=q.device)
-    st = _lib.lib().cvllm_prefill_attn(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-        k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), lens.data_ptr(), pt.data_ptr(), bm.data_ptr(),
-        cu.data_ptr(), B, N, int(max_seqlen_q), HQ, HKV, D, int(PAGE_SIZE), pt.shape[-1], float(sm_scale),
-        _lib.dtype_code(q.dtype), _lib.stream(),
-    )
-    _lib.check(st, "cvllm_prefill_attn")
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+            k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), lens.data_ptr(), pt.data_ptr(), bm.data_ptr(),
+            cu.data_ptr(), B, N, int(max_seqlen_q), HQ, HKV, D, int(PAGE_SIZE), pt.shape[-1], float(sm_scale),
+            _lib.dtype_code(q.dtype), _lib.stream())
+    if k_cache.dtype == _lib.FP8:
+        assert v_cache.dtype == _lib.FP8
+        _lib.check_fp8_scales(k_cache, k_scale, v_scale)
+        st = _lib.lib().cvllm_prefill_attn_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr())
+        _lib.check(st, "cvllm_prefill_attn_fp8")
+    else:
+        st = _lib.lib().cvllm_prefill_attn(*args)
+        _lib.check(st, "cvllm_prefill_attn")
     return out

@@ -158,19 +158,24 @@ def compact_cache_inplace(
     k_cache: torch.Tensor,
     v_cache: torch.Tensor,
     PAGE_SIZE: int,
+    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    v_scale: torch.Tensor | None = None,
 ) -> None:
     """Move the kept rows of every (b, h) down inside the paged cache (last chunk of a chunked prefill): the same final
-    cache as `extract_and_store_top_kv` fed with the whole sequence's packed keys / values."""
+    cache as `extract_and_store_top_kv` fed with the whole sequence's packed keys / values.  On an FP8 cache a row's
+    codes and its two scales move together (nothing is re-quantised)."""
     _lib.require_cuda(kept_idx, new_lens, dst_base, src_base, page_table, batch_mapping, k_cache, v_cache)
-    if k_cache.dtype == _lib.FP8:
-        raise NotImplementedError("in-place compaction has no FP8 form (chunked prefill is off with an FP8 cache)")
     B, H, max_len = kept_idx.shape
-    st = _lib.lib().cvllm_compact_cache_inplace(
-        kept_idx.data_ptr(), new_lens.data_ptr(), _lib.i32(dst_base).data_ptr(), _lib.i32(src_base).data_ptr(),
-        page_table.data_ptr(), _lib.i32(batch_mapping).data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), B, H,
-        k_cache.shape[-1], int(max_len), int(PAGE_SIZE), page_table.shape[-1], _lib.dtype_code(k_cache.dtype),
-        _lib.stream())
-    _lib.check(st, "cvllm_compact_cache_inplace")
+    args = (kept_idx.data_ptr(), new_lens.data_ptr(), _lib.i32(dst_base).data_ptr(), _lib.i32(src_base).data_ptr(),
+            page_table.data_ptr(), _lib.i32(batch_mapping).data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), B, H,
+            k_cache.shape[-1], int(max_len), int(PAGE_SIZE), page_table.shape[-1])
+    if k_cache.dtype == _lib.FP8:
+        _lib.check_fp8_scales(k_cache, k_scale, v_scale)
+        st = _lib.lib().cvllm_compact_cache_inplace_fp8(*args, _lib.stream(), k_scale.data_ptr(), v_scale.data_ptr())
+        _lib.check(st, "cvllm_compact_cache_inplace_fp8")
+    else:
+        st = _lib.lib().cvllm_compact_cache_inplace(*args, _lib.dtype_code(k_cache.dtype), _lib.stream())
+        _lib.check(st, "cvllm_compact_cache_inplace")
 
 
 def scores_to_retain_indices(

@@ -51,7 +51,11 @@ def _chunked_post_rope(q, k, context):
         pos = torch.arange(ch.start, device=k.device)
         pages = attn.page_table[context.batch_mapping[0].long()].long()  # [HKV, P] of the sequence's row
         rows = pages[:, pos // attn.page_size] * attn.page_size + (pos % attn.page_size)[None, :]  # [HKV, start]
-        k_all[: ch.start] = attn.k_cache[rows].transpose(0, 1)
+        if attn.k_cache.dtype == _lib.FP8:  # the prefill kernel's read-back rule: (fp32(code) * scale) rounded to k.dtype
+            codes = attn.k_cache.view(torch.uint8)[rows].view(_lib.FP8)
+            k_all[: ch.start] = (codes.float() * attn.k_scale[rows][..., None]).to(k.dtype).transpose(0, 1)
+        else:
+            k_all[: ch.start] = attn.k_cache[rows].transpose(0, 1)
     k_all[ch.start :] = k
     cu_k = torch.tensor([0, ch.total_len], dtype=torch.int32).to(k.device, non_blocking=True)
     return query_aware_key_scores(q, k_all, context.cu_seqlens_q, cu_k, w=32, max_seqlen_k=ch.total_len)

@@ -33,6 +33,9 @@ class LLMConfig:
     attention_backend: AttentionBackend = AttentionBackend.COMPACTOR_TRITON
     show_progress_bar: bool = True
     kv_cache_dtype: str = "auto"  # "auto" = the model dtype; "fp8_e4m3" = e4m3 codes + one fp32 scale per cache row
+    # FP8 cache only: prefill attention reads the FP8 prefix (cvllm_prefill_attn_fp8), which turns chunked prefill and
+    # prefix reuse on.  Opt-in for now; without it an FP8 cache refuses both, as before.
+    fp8_prefix_reads: bool = False
 
     def __post_init__(self):
         if self.kv_cache_dtype not in ("auto", "fp8_e4m3"):

@@ -48,8 +48,9 @@ class KVCacheManager:
         self.chunked_prefill = True  # prompts longer than max_batched_tokens are prefilled in chunks (scheduler.py)
         self.fp8 = getattr(config, "kv_cache_dtype", "auto") == "fp8_e4m3"
         self.cache_dtype = torch.float8_e4m3fn if self.fp8 else self.model_dtype
-        if self.fp8:
-            self.chunked_prefill = False  # the prefill kernel cannot read an FP8 prefix
+        self.fp8_prefix_reads = self.fp8 and bool(getattr(config, "fp8_prefix_reads", False))
+        if self.fp8 and not self.fp8_prefix_reads:
+            self.chunked_prefill = False  # FP8 prefix reads in prefill attention are opt-in (LLMConfig.fp8_prefix_reads)
 
     # ---- sizing ------------------------------------------------------------------------------------------------
     def bytes_per_page_all_layers(self) -> int:

@@ -156,9 +156,9 @@ class ModelRunner:
         from ..compression.compression_config import SequenceCompressionParams
         from ..config.sampling_params import SamplingParams
 
-        if self.kv_manager.fp8:
-            raise NotImplementedError("prefix reuse needs prefill attention over cached rows, which cannot read an FP8 "
-                                      "cache (kv_cache_dtype='fp8_e4m3')")
+        if self.kv_manager.fp8 and not self.kv_manager.fp8_prefix_reads:
+            raise NotImplementedError("prefix reuse on an FP8 cache (kv_cache_dtype='fp8_e4m3') needs prefill attention "
+                                      "over FP8 rows: set LLMConfig.fp8_prefix_reads=True")
         params = batch_compression_params if batch_compression_params is not None else BatchCompressionParams()
         method, chunk = self._scoring_key(params)
         P = (len(token_ids) // PREFIX_ALIGN) * PREFIX_ALIGN
@@ -203,8 +203,8 @@ class ModelRunner:
 
     @torch.inference_mode()
     def run_prefill_with_prefix(self, a: PrefillBatchArguments, batch_mapping: torch.Tensor, entry: PrefixEntry) -> torch.Tensor:
-        """The request's row receives a copy of the prefix's K/V pages (every layer, every head), its lengths start at
-        P, and the suffix runs as the remaining chunk(s) of a chunked prefill whose scoring state starts from the
+        """The request's row receives a copy of the prefix's K/V pages (every layer, every head; on an FP8 cache the codes
+        and the scales), its lengths start at P, and the suffix runs as the remaining chunk(s) of a chunked prefill whose scoring state starts from the
         prefix's stash."""
         cache = self.kv_manager.paged_cache
         P, PS = entry.length, cache.page_size
@@ -213,9 +213,14 @@ class ModelRunner:
         L, H = cache.num_layers, cache.H_kv
         src = cache.page_table[:, entry.row, :, :npg].long()  # [L, H, npg] physical pages
         dst = cache.page_table[:, row, :, :npg].long()
-        kv = cache.kv_cache.view(2, L, cache.n_pages, PS, cache.head_dim)
+        # bytes are copied (an FP8 cache as uint8), and an FP8 cache's scale pages go along with its code pages
+        raw = cache.kv_cache.view(torch.uint8) if cache.kv_scale is not None else cache.kv_cache
+        kv = raw.view(2, L, cache.n_pages, PS, cache.head_dim)
         li = torch.arange(L, device=src.device)[:, None, None].expand_as(src)
         kv[:, li, dst] = kv[:, li, src]
+        if cache.kv_scale is not None:
+            sc = cache.kv_scale.view(2, L, cache.n_pages, PS)
+            sc[:, li, dst] = sc[:, li, src]
         cache.bh_seq_lens[:, row] = P
         total = int(a.context_lens[0])
         state = ChunkedPrefillState(total, self.num_kv_heads, attention_modules(self.model))

@@ -80,8 +80,6 @@ class Attention(nn.Module):
         common = dict(self._cache_args(), batch_mapping=batch_mapping, bh_lens=seq_lens,
                       STORE_STREAM=context.STORE_STREAM)
         chunk = getattr(context, "chunk", None)
-        # FP8 cache: the prefill kernel below never reads the cache (the cached prefix is empty: no chunks, no prefix reuse)
-        assert not self._fp8 or chunk is None, "chunked prefill cannot read an FP8 cache"
         compress = context.do_compression and scores is not None and chunk is None
         if compress:
             cc = context.compression_context
@@ -98,7 +96,7 @@ class Attention(nn.Module):
             q, k, v, self.k_cache, self.v_cache, seq_lens_bh=lengths_before, global_page_table=self.page_table,
             batch_mapping=batch_mapping, cu_seqlens_q=context.cu_seqlens_q, max_seqlen_q=context.max_seqlen_q,
             max_seqlen_k_cache=context.max_bh_len, HKV=int(self.num_kv_heads), PAGE_SIZE=self.page_size,
-            sm_scale=self.scale)
+            sm_scale=self.scale, k_scale=self.k_scale, v_scale=self.v_scale)
         if chunk is not None and chunk.is_last and context.do_compression and scores is not None:
             # last chunk of a chunked prefill: the whole prompt now sits in the cache uncompressed; select over the
             # whole sequence's scores and compact the cache in place.  Enqueued on the store stream BEHIND the attention
@@ -116,7 +114,7 @@ class Attention(nn.Module):
         kept, new_lens = select_retained(scores, cu, chunk.total_len, cc.batch_tokens_to_retain, context.batch_mapping,
                                          base, self.page_size, True)
         compact_cache_inplace(kept, new_lens, base, base, self.page_table, context.batch_mapping, self.k_cache,
-                              self.v_cache, self.page_size)
+                              self.v_cache, self.page_size, k_scale=self.k_scale, v_scale=self.v_scale)
         seq_lens.copy_(new_lens)  # written back to the layer's table by forward() on the same stream
 
     def _decode_reference_order(self, context: Context, q, k, v, seq_lens):

@@ -171,6 +171,79 @@ __global__ __launch_bounds__(256) void compact_store_fp8_kernel(
   }
 }
 
+// ---- compaction IN PLACE (last chunk of a chunked prefill on an FP8 cache) --------------------------------------------------
+// Sibling of compact_inplace_kernel (store_kv.hip): the kept rows of every (b,h) move down to slots dst_base.. in token
+// order; a row's D bytes of codes and its two fp32 scales move together and nothing is re-quantised, so the result is
+// what compact_store_fp8_kernel writes from the packed 16-bit rows, bit for bit.  The no-overlap argument is that
+// kernel's: with an ascending kept list slot j receives the row of token t_j >= j, tile i writes slots below
+// dst_base + TILE (i + 1) and every source of a later tile lies at or above src_base + TILE (i + 1); inside a tile a
+// barrier separates all loads from all stores, and the next tile's loads are issued before this tile's stores.
+// A row is D bytes here, not 2 D: D / 16 lanes of 16 B; every lane of a row carries the row's two scales, lane 0 writes them.
+template <int D>
+__global__ __launch_bounds__(256) void compact_inplace_fp8_kernel(
+    const int* __restrict__ kept_idx, const int* __restrict__ new_lens, const int* __restrict__ dst_base,
+    const int* __restrict__ src_base, const int* __restrict__ page_table, const int* __restrict__ bmap,
+    uint8_t* __restrict__ kc, uint8_t* __restrict__ vc, float* __restrict__ ksc, float* __restrict__ vsc, int H,
+    int max_seqlen, int PS, int NLP) {
+  constexpr int LPR = D / 16;         // lanes per row
+  constexpr int RPP = 256 / LPR;      // rows per pass of the workgroup
+  constexpr int TILE = 128;           // rows per tile, as the 16-bit kernel at D = 128
+  constexpr int PASSES = TILE / RPP;  // rows per thread and tile
+  const int bh = blockIdx.x;
+  const int b = bh / H, h = bh % H;
+  const int d0 = dst_base[bh], s0 = src_base[bh];
+  const int cnt = new_lens[bh] - d0;
+  const int tok_max = NLP * PS - 1 - s0;  // last row the page table can address
+  const int dl = threadIdx.x % LPR, rl = threadIdx.x / LPR;
+  const int* list = kept_idx + (size_t)bh * max_seqlen;
+  const int* pt = page_table + ((size_t)bmap[b] * H + h) * NLP;
+  auto row_of = [&](int pos) { return (size_t)pt[pos / PS] * PS + pos % PS; };
+  struct Rows {
+    uint4 k[PASSES], v[PASSES];
+    float ks[PASSES], vs[PASSES];
+  };
+  Rows buf[2];
+  auto load_tile = [&](int t0, Rows& x) {
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      const int j = t0 + p * RPP + rl;
+      if (j < cnt) {
+        const size_t a = row_of(s0 + max(0, min(list[j], tok_max)));  // clamped: see compact_store_kernel
+        x.k[p] = *reinterpret_cast<const uint4*>(kc + a * D + dl * 16);
+        x.v[p] = *reinterpret_cast<const uint4*>(vc + a * D + dl * 16);
+        x.ks[p] = ksc[a];
+        x.vs[p] = vsc[a];
+      }
+    }
+  };
+  auto store_tile = [&](int t0, const Rows& x) {
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      const int j = t0 + p * RPP + rl;
+      if (j < cnt) {
+        const size_t a = row_of(d0 + j);
+        *reinterpret_cast<uint4*>(kc + a * D + dl * 16) = x.k[p];
+        *reinterpret_cast<uint4*>(vc + a * D + dl * 16) = x.v[p];
+        if (dl == 0) {
+          ksc[a] = x.ks[p];
+          vsc[a] = x.vs[p];
+        }
+      }
+    }
+  };
+  if (cnt <= 0) return;
+  load_tile(0, buf[0]);
+  for (int t0 = 0; t0 < cnt; t0 += 2 * TILE) {
+    if (t0 + TILE < cnt) load_tile(t0 + TILE, buf[1]);
+    __syncthreads();  // every row of tile t0 is in registers (the barrier also drains each wave's loads)
+    store_tile(t0, buf[0]);
+    if (t0 + TILE >= cnt) break;
+    if (t0 + 2 * TILE < cnt) load_tile(t0 + 2 * TILE, buf[0]);
+    __syncthreads();
+    store_tile(t0 + TILE, buf[1]);
+  }
+}
+
 // ---- decode attention --------------------------------------------------------------------------------------------------
 template <int N>
 __device__ __forceinline__ void vm_wait() {
@@ -641,6 +714,27 @@ extern "C" int cvllm_compact_store_fp8(const void* new_keys, const void* new_val
                        cu_seqlens_k, bh_lens0, page_table, batch_mapping, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale,
                        v_scale, H, max_seqlen, page_size, n_logical_pages_max, tiles);
   });
+  return check_launch();
+}
+
+extern "C" int cvllm_compact_cache_inplace_fp8(const int32_t* kept_idx, const int32_t* new_lens, const int32_t* dst_base,
+                                              const int32_t* src_base, const int32_t* page_table,
+                                              const int32_t* batch_mapping, void* k_cache, void* v_cache, int B, int H,
+                                              int D, int max_seqlen, int page_size, int n_logical_pages_max,
+                                              cvllm_stream_t stream, float* k_scale, float* v_scale) {
+  if (!kept_idx || !new_lens || !dst_base || !src_base || !page_table || !batch_mapping || !k_cache || !v_cache ||
+      !k_scale || !v_scale)
+    return CVLLM_ERR_ARG;
+  if (B <= 0 || H <= 0 || max_seqlen <= 0 || page_size <= 0 || n_logical_pages_max <= 0) return CVLLM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+#define CI_CALL(D_)                                                                                                  \
+  hipLaunchKernelGGL((compact_inplace_fp8_kernel<D_>), dim3(B* H), dim3(256), 0, st, kept_idx, new_lens, dst_base,     \
+                     src_base, page_table, batch_mapping, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, H, \
+                     max_seqlen, page_size, n_logical_pages_max)
+  if (D == 64) CI_CALL(64);
+  else if (D == 128) CI_CALL(128);
+  else return CVLLM_ERR_SHAPE;
+#undef CI_CALL
   return check_launch();
 }
 

@@ -327,6 +327,28 @@ int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const void* v_cach
                           const int32_t* batch_mapping, void* workspace, size_t workspace_bytes, int B, int HQ,
                           int HKV, int D, int page_size, int n_logical_pages_max, float sm_scale, int n_splits,
                           int dtype, cvllm_stream_t stream);
+/* FP8 cache, in-place compaction: cvllm_compact_cache_inplace on e4m3 codes.  A kept row's D bytes of codes and its
+ * two scales move together, nothing is re-quantised: the same bits as cvllm_compact_store_fp8 fed with the packed
+ * 16-bit rows.  D in {64, 128}. */
+int cvllm_compact_cache_inplace_fp8(const int32_t* kept_idx, const int32_t* new_lens,
+                                    const int32_t* dst_base, const int32_t* src_base,
+                                    const int32_t* page_table, const int32_t* batch_mapping,
+                                    void* k_cache, void* v_cache, int B, int H, int D, int max_seqlen,
+                                    int page_size, int n_logical_pages_max, cvllm_stream_t stream,
+                                    float* k_scale, float* v_scale);
+
+/* FP8 cache, prefill attention: cvllm_prefill_attn over [e4m3 cached prefix || 16-bit appended block]
+ * (csrc/prefill_fp8.hip).  k_cache / v_cache hold e4m3 codes, k_scale / v_scale [cache_rows] fp32 are indexed like the
+ * codes; q, k, v, out stay f16 / bf16.  A cached element is read back as rne_T(fp32(code) * scale), T = the model dtype.
+ * D in {64, 128}, HQ / HKV in {1, 2, 4, 8}, any page size, any n_logical_pages_max; anything else CVLLM_ERR_SHAPE. */
+int cvllm_prefill_attn_fp8(const void* q, const void* k, const void* v, int64_t sq_n, int64_t sk_n,
+                           int64_t sk_h, int64_t sv_n, int64_t sv_h, const void* k_cache,
+                           const void* v_cache, void* out, const int32_t* seq_lens_bh,
+                           const int32_t* page_table, const int32_t* batch_mapping,
+                           const int32_t* cu_seqlens_q, int B, int total_tokens, int max_seqlen_q,
+                           int HQ, int HKV, int D, int page_size, int n_logical_pages_max,
+                           float sm_scale, int dtype, cvllm_stream_t stream, const float* k_scale,
+                           const float* v_scale);
 
 #ifdef __cplusplus
 }

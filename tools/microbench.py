@@ -100,18 +100,24 @@ def bench_prefill(args):
             v = qkv[:, (HQ + HKV) * D:].view(N, HKV, D)
             if args.fused_v > 1:
                 k = qkv[:, HQ * D:(HQ + HKV) * D].view(N, HKV, D)
-        kc = torch.zeros(PS, D, device=dev, dtype=dtype)
-        lens = torch.zeros(B, HKV, dtype=torch.int32, device=dev)
-        pt = torch.zeros(B + 1, HKV, 1, dtype=torch.int32, device=dev)
-        bm = torch.arange(1, B + 1, dtype=torch.int32, device=dev)
+        Pc = args.prefix  # cached prefix rows per head in front of the L appended tokens
+        caches, pt, bm, lens = build_cache(B, HKV, D, PS, max(Pc, 1), dtype, dev)
+        kc, vc = caches[0]
+        lens.fill_(Pc)
+        scales = {}
+        if args.kv_dtype == "fp8":  # e4m3 codes + one fp32 scale per row: cvllm_prefill_attn_fp8 (csrc/prefill_fp8.hip)
+            kc, vc = kc.to(torch.float8_e4m3fn), vc.to(torch.float8_e4m3fn)
+            scales = dict(k_scale=torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005,
+                          v_scale=torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005)
         cu = torch.arange(0, B + 1, dtype=torch.int32, device=dev) * L
-        fn = lambda: causal_sparse_varlen_with_cache(q, k, v, kc, kc, lens, pt, bm, cu, L, 0, HKV, PS)
+        fn = lambda: causal_sparse_varlen_with_cache(q, k, v, kc, vc, lens, pt, bm, cu, L, Pc, HKV, PS, **scales)
         # warm until ~40 ms of this kernel have run: with 2 warm launches a 16 K kernel (2 ms) was still timed on a ramping
         # clock (2.30 ms against 2.03 steady, profiles/r02_prefill_workgroup_stamps.txt)
-        warm = max(2, min(40, int(40e-3 / (4e-9 * 2 * L * L / 2 * B / 1e3 + 1e-4))))
+        warm = max(2, min(40, int(40e-3 / (4e-9 * 2 * L * (L / 2 + Pc) * B / 1e3 + 1e-4))))
         us = time_fn(fn, iters=max(5, warm // 2), warmup=warm)
-        flops = 4 * D * HQ * B * (L * (L + 1) / 2)
-        print(f"prefill B={B} L={L}: {us / 1e3:9.3f} ms  {flops / us / 1e6:8.1f} TFLOP/s (causal flops)", flush=True)
+        flops = 4 * D * HQ * B * (L * Pc + L * (L + 1) / 2)
+        print(f"prefill{' kv=fp8' if scales else ''} B={B} L={L} prefix={Pc}: {us / 1e3:9.3f} ms  "
+              f"{flops / us / 1e6:8.1f} TFLOP/s (causal flops)", flush=True)
 
 
 def bench_scoring(args):
@@ -186,7 +192,8 @@ if __name__ == "__main__":
     ap.add_argument("--variant", type=int, default=-1)
     ap.add_argument("--fused-v", type=int, default=0, help="prefill: 1 = V (2 = K and V) as strided views of a fused qkv buffer")
     ap.add_argument("--kv-dtype", choices=["model", "fp8"], default="model",
-                    help="decode: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
+                    help="decode, prefill: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
+    ap.add_argument("--prefix", type=int, default=0, help="prefill: cached prefix rows per head in front of the --L appended tokens")
     ap.add_argument("--flush", action="store_true", help="decode: a 128 MB device copy between launches (cold metadata, as inside a decode step)")
     ap.add_argument("--iters", type=int, default=0)      # scoring: timed calls per item (0 = default)
     ap.add_argument("--warmup", type=int, default=-1)    # scoring: warm calls per item (-1 = default)
