@@ -61,6 +61,8 @@ SIGNATURES = {
     "cvllm_compact_store_fp8": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
                                      _I, _I, _P, _P, _P]),
     "cvllm_decode_attn_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
+    "cvllm_decode_append_attn_fp8": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I,
+                                          _I, _F, _I, _I, _I, _P, _P, _P]),
     "cvllm_compact_cache_inplace_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cvllm_prefill_attn_fp8": (_I, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
                                     _I, _I, _I, _F, _I, _P, _P, _P]),

@@ -199,12 +199,18 @@ def fused_decode_step(
     key_split: int = None,
     reserved_batch: int = 0,
     max_len_hint: int = 0,
+    *,
+    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    v_scale: torch.Tensor | None = None,
 ):
     """decode_store_kv + head_sparse_decode_attention + length write-back of the reference's decode branch
-    (layers/attention.py:127-160) in one C-ABI call that works directly on the layer's length table."""
+    (layers/attention.py:127-160) in one C-ABI call that works directly on the layer's length table.  On an FP8 cache
+    the new row is quantised in the attention kernel (csrc/kv_fp8.hip): the same bits as the separate calls."""
     _lib.require_cuda(q, key, value, k_cache, v_cache, bh_seq_lens_layer, page_table, batch_mapping)
-    if k_cache.dtype == _lib.FP8:
-        raise NotImplementedError("no fused append on an FP8 cache: decode_store_kv, then head_sparse_decode_attention")
+    fp8 = k_cache.dtype == _lib.FP8
+    if fp8:
+        assert v_cache.dtype == _lib.FP8
+        _lib.check_fp8_scales(k_cache, k_scale, v_scale)
     B, HQ, D = q.shape
     assert key.shape == (B, HKV, D) and value.shape == (B, HKV, D)
     if not q.is_contiguous():
@@ -224,13 +230,17 @@ def fused_decode_step(
     if n_splits > 1:
         ws_bytes = L.cvllm_decode_workspace_bytes(B, HQ, D, n_splits)
         ws = _workspace(q.device, ws_bytes)
-    st = L.cvllm_decode_append_attn(
+    args = (
         q.data_ptr(), key.data_ptr(), value.data_ptr(), key.stride(0), key.stride(1), value.stride(0), value.stride(1),
         k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), bh_seq_lens_layer.data_ptr(), page_table.data_ptr(),
         batch_mapping.data_ptr(), _lib.ptr(ws), ws_bytes, B, HQ, HKV, D, PAGE_SIZE, n_lp, float(sm_scale), n_splits,
         int(reserved_batch), _lib.dtype_code(q.dtype), _lib.stream(),
     )
-    _lib.check(st, "cvllm_decode_append_attn")
+    if fp8:
+        _lib.check(L.cvllm_decode_append_attn_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr()),
+                   "cvllm_decode_append_attn_fp8")
+    else:
+        _lib.check(L.cvllm_decode_append_attn(*args), "cvllm_decode_append_attn")
     return out
 
 

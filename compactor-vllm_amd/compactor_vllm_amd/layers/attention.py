@@ -131,13 +131,15 @@ class Attention(nn.Module):
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scores: Optional[torch.Tensor] = None):
         context: Context = get_context()
         batch_mapping = context.batch_mapping
-        if not context.is_prefill and self.fused_decode and self.bh_seq_lens is not None and not self._fp8:
+        if not context.is_prefill and self.fused_decode and self.bh_seq_lens is not None:
             # store-then-attend directly on the layer's length table: one C-ABI call instead of
-            # index_select + decode_store_kv + attention + index_copy_ (same results, 3 fewer launches)
+            # index_select + decode_store_kv + attention + index_copy_ (same results, 3 fewer launches); with an
+            # FP8 cache the attention kernel quantises the new row itself
             assert self.k_cache is not None, "KV Cache must be initialized for decoding"
             return fused_decode_step(q, k, v, self.k_cache, self.v_cache, self.bh_seq_lens, self.page_table,
                                      batch_mapping, int(self.num_kv_heads), self.page_size, self.scale,
-                                     key_split=context.key_split, max_len_hint=context.decode_len_hint)
+                                     key_split=context.key_split, max_len_hint=context.decode_len_hint,
+                                     k_scale=self.k_scale, v_scale=self.v_scale)
         seq_lens = self._gathered_lengths(batch_mapping)
         if context.is_prefill:
             o = self._prefill(context, q, k, v, scores, seq_lens)

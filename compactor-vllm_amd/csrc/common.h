@@ -108,10 +108,13 @@ int store_decode_kv_impl(const void* key, const void* value, int64_t sk_b, int64
 
 // decode_attn.hip: the split-merge workspace starts with a header (word 0 = in-launch merge error flag, the rest reserved
 // and zero); behind it the two-kernel path keeps part_o[B,S,HQ,D] then part_lse[B,S,HQ] (fp32).  launch_decode_stage2
-// merges them into out[B,HQ,D] and hands the words it read back zeroed (kv_fp8.hip's stage 1 uses it too).
+// merges them into out[B,HQ,D] and hands the words it read back zeroed (kv_fp8.hip's stage 1 uses it too).  With
+// lens_by_row != nullptr it also publishes the fused append: lens_by_row[bmap[b], h] += 1 for every (b, kv-head) whose
+// row is not `reserved` (the layer's [Bmax+1, HQ/G] table).
 constexpr size_t DEC_WS_HEADER = 256;
 int launch_decode_stage2(float* part_o, float* part_lse, void* out, int B, int HQ, int D, int S, int dtype,
-                         hipStream_t stream);
+                         hipStream_t stream, int* lens_by_row = nullptr, const int* bmap = nullptr, int G = 1,
+                         int reserved = -1);
 
 // dynamic-LDS limit of a kernel, set once per (kernel instantiation, device): the attribute lives on the device's
 // code object, so a second device in the same process needs its own call

@@ -1038,14 +1038,16 @@ __global__ __launch_bounds__(256) void decode_merge_shards_kernel(const uint16_t
   *reinterpret_cast<uint4*>(out + (size_t)row * D + 8 * c) = o;
 }
 
-// stage 2 on its own (no fused append, no LSE output): the merge of kv_fp8.hip's stage-1 partials
+// stage 2 on its own (no LSE output): the merge of kv_fp8.hip's stage-1 partials; lens_by_row != nullptr: its fused
+// append, whose L_old + 1 this kernel publishes in the layer's table
 int launch_decode_stage2(float* part_o, float* part_lse, void* out, int B, int HQ, int D, int S, int dtype,
-                         hipStream_t stream) {
+                         hipStream_t stream, int* lens_by_row, const int* bmap, int G, int reserved) {
   if (D != 64 && D != 128) return CVLLM_ERR_SHAPE;
   const dim3 grid(B * HQ), block(256);
+  const int append = lens_by_row != nullptr ? 1 : 0;
 #define CVLLM_STAGE2(T_, D_)                                                                                          \
   hipLaunchKernelGGL((decode_stage2_kernel<T_, D_>), grid, block, 0, stream, part_o, part_lse, (uint16_t*)out, HQ, S, \
-                     (int*)nullptr, (const int*)nullptr, 1, 0, 0, -1, (float*)nullptr)
+                     lens_by_row, bmap, G, append, append, reserved, (float*)nullptr)
   if (dtype == CVLLM_F16) {
     if (D == 64) CVLLM_STAGE2(F16, 64); else CVLLM_STAGE2(F16, 128);
   } else if (dtype == CVLLM_BF16) {

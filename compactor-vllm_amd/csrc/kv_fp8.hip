@@ -33,6 +33,18 @@
 //     global side and conflict-free for both the 16 B row reads of K and the transposing reads of V.
 // Splits are merged by decode_stage2_kernel (decode_attn.hip) from normalised fp32 partials + LSE; one split writes
 // the output directly.  No in-launch merge.
+//
+// Fused append (decode_fp8_kernel<.., APPEND = true>, cvllm_decode_append_attn_fp8): the contract of the 16-bit fused
+// append (decode_attn.hip).  The new token's row of (b, h) belongs at position L_old; every workgroup works with
+// L = L_old + 1.  Row L_old lies in one 32-row unit of one split: the wave that owns that unit is the only one that
+// touches the row.  Every wave quantises the new K row (lanes 0..D/16-1) and V row (lanes 8..8+D/16-1) up front with
+// quant_row - ordinary loads, retired before the first LDS-DMA.  The owner lets the unit's DMA land (it fetched the
+// slot's stale bytes), then patches the unit's LDS image with ds_write - D code bytes of K and of V at the swizzled
+// chunk positions, the two scales in the scale block - and runs the unit through the unchanged MFMA path: bit-identical
+// to store-then-attend.  As its last act it writes codes and scales to the paged cache with vector stores; no other
+// workgroup reads that slot in this launch.  L_old + 1 is published by the workgroup itself with one split (after the
+// barrier in front of the wave merge: every wave has read L_old) and by decode_stage2_kernel otherwise; stage 1 never
+// writes a length when stage 2 follows.
 #include "common.h"
 
 namespace cvllm {
@@ -51,10 +63,11 @@ __device__ __forceinline__ float group_allreduce_max(float v) {
 }
 
 // ---- the shared row writer -------------------------------------------------------------------------------------------
-// Called together by the D/16 lanes of a row; `src` = the lane's 16 source elements, `codes` = the lane's 16 B.
+// Called together by the D/16 lanes of a row, which must be aligned inside a 16-lane DPP row; `src` = the lane's 16
+// source elements.  quant_row leaves the lane's 16 B of codes in `c` and returns the row's scale (the same in every lane
+// of the row); quant_row_store also writes them (`codes` = the lane's 16 B).
 template <typename T, int D>
-__device__ __forceinline__ void quant_row_store(const uint16_t* __restrict__ src, uint8_t* __restrict__ codes,
-                                                float* __restrict__ scale_dst, bool first_lane) {
+__device__ __forceinline__ float quant_row(const uint16_t* __restrict__ src, uint4& c) {
   constexpr int LPR = D / 16;
   const uint4 u0 = *reinterpret_cast<const uint4*>(src), u1 = *reinterpret_cast<const uint4*>(src + 8);
   const uint32_t w[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
@@ -70,14 +83,22 @@ __device__ __forceinline__ void quant_row_store(const uint16_t* __restrict__ src
   a = fmaxf(group_allreduce_max<LPR>(a), 1e-30f);
   const float scale = __fdiv_rn(a, 448.f);
   const float inv = __fdiv_rn(448.f, a);
-  uint32_t c[4];
+  uint32_t cw[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     int p = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * i] * inv, x[4 * i + 1] * inv, 0, false);
     p = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * i + 2] * inv, x[4 * i + 3] * inv, p, true);
-    c[i] = (uint32_t)p;
+    cw[i] = (uint32_t)p;
   }
-  *reinterpret_cast<uint4*>(codes) = make_uint4(c[0], c[1], c[2], c[3]);
+  c = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+  return scale;
+}
+template <typename T, int D>
+__device__ __forceinline__ void quant_row_store(const uint16_t* __restrict__ src, uint8_t* __restrict__ codes,
+                                                float* __restrict__ scale_dst, bool first_lane) {
+  uint4 c;
+  const float scale = quant_row<T, D>(src, c);
+  *reinterpret_cast<uint4*>(codes) = c;
   if (first_lane) *scale_dst = scale;
 }
 
@@ -325,12 +346,21 @@ constexpr size_t fp8_ring_bytes() {
   return (size_t)F8_NW * R * (2 * F8_UR * D + 256);
 }
 
-template <typename T, int D, int R>
+// the appended row of the fused append; unused (and never read) without APPEND
+struct Fp8NewRow {
+  const uint16_t *key, *val;  // [B, HKV, D] in the model dtype
+  int64_t sk_b, sk_h, sv_b, sv_h;
+  int reserved;
+};
+
+// APPEND: seq_lens is the layer's full [Bmax+1, HKV] table indexed by bmap[b] (lengths BEFORE the append); otherwise the
+// gathered [B, HKV] table.  The caches and scales are written with APPEND only.
+template <typename T, int D, int R, bool APPEND>
 __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
-    const uint16_t* __restrict__ q, const uint8_t* __restrict__ kc, const uint8_t* __restrict__ vc,
-    const float* __restrict__ ksc, const float* __restrict__ vsc, const int* __restrict__ seq_lens,
-    const int* __restrict__ page_table, const int* __restrict__ bmap, uint16_t* __restrict__ out,
-    float* __restrict__ part_o, float* __restrict__ part_lse, int HKV, int G, int PS, int NLP, int S, float scale) {
+    const uint16_t* __restrict__ q, uint8_t* __restrict__ kc, uint8_t* __restrict__ vc, float* __restrict__ ksc,
+    float* __restrict__ vsc, int* __restrict__ seq_lens, const int* __restrict__ page_table,
+    const int* __restrict__ bmap, uint16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_lse,
+    int HKV, int G, int PS, int NLP, int S, float scale, Fp8NewRow nr) {
   constexpr int NW = F8_NW, UR = F8_UR;
   constexpr int CPR = D / 16;            // 16 B chunks per row
   constexpr int RPWIN = 256 / D;         // rows per 256 B of LDS (one pass over all banks)
@@ -362,7 +392,10 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
   const int g = lane >> 4;  // lane quarter
 
   const int bt = bmap[b];
-  const int L = seq_lens[bh];
+  const int lidx = APPEND ? bt * HKV + h : bh;
+  const int L_old = seq_lens[lidx];
+  const bool append = APPEND && bt != nr.reserved;
+  const int L = APPEND ? (append ? L_old + 1 : 0) : L_old;  // a reserved row attends to nothing and stores nothing
   // rows are dealt to the S splits in whole units, as decode_fused_kernel does
   const int U = (L + UR - 1) / UR;
   const int start = (int)(((long long)s * U) / S) * UR;
@@ -387,6 +420,24 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
     if (j < G)
       v = *reinterpret_cast<const uint4*>(q + ((size_t)b * HQ + h * G + j) * D + (g * KCH + m / 2) * 16 + (m % 2) * 8);
     qb[m] = __builtin_bit_cast(s16x8, v);
+  }
+
+  // Fused append.  Every wave quantises the new row, nothing diverges: in each 16-lane row lanes 0..CPR-1 take K and lanes
+  // 8..8+CPR-1 take V, chunk nr_dl each (at D = 64 lanes 4-7 and 12-15 repeat them in DPP groups of their own).
+  const int nr_v = (lane >> 3) & 1, nr_dl = lane & (CPR - 1);
+  const bool nr_lane = lane < 16 && (lane & 7) < CPR;  // the lanes that write the row
+  uint4 nr_codes = make_uint4(0u, 0u, 0u, 0u);
+  float nr_scale = 0.f;
+  int own_jw = -1;      // wave-local index of the unit that holds row L_old, in the one wave that owns it
+  size_t own_prow = 0;  // the row's physical cache row, known when that unit is issued
+  if constexpr (APPEND) {
+    const uint16_t* src = nr_v ? nr.val + b * nr.sv_b + h * nr.sv_h : nr.key + b * nr.sk_b + h * nr.sk_h;
+    nr_scale = quant_row<T, D>(src + nr_dl * 16, nr_codes);
+    if (append && L_old >= start && L_old < end) {
+      const int u = (L_old - start) / UR;
+      if (u % NW == wave) own_jw = u / NW;
+    }
+    asm volatile("" : "+v"(nr_codes.x), "+v"(nr_codes.y), "+v"(nr_codes.z), "+v"(nr_codes.w), "+v"(nr_scale));
   }
 
   const int* pt = page_table + ((size_t)bt * HKV + h) * NLP;
@@ -451,6 +502,8 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
       for (int jj = 0; jj < F8_PGREGS; ++jj) asm volatile("" : "+v"(pgreg[jj]));
     }
     const size_t prow = (size_t)page_of(lpi_rel) * PS + row0 % PS;
+    if constexpr (APPEND)
+      if (jw == own_jw) own_prow = prow + (L_old - row0);  // kept: the page-id window may have moved on by then
     const uint8_t* kp = kc + prow * D;
     const uint8_t* vp = vc + prow * D;
     char* slot = ring + (jw % R) * UNIT_BYTES;
@@ -487,6 +540,21 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
     }
     const uint32_t sl = ring_lds + (jw % R) * UNIT_BYTES;
     const int row0 = start + (wave + jw * NW) * UR;
+
+    if constexpr (APPEND) {
+      // The unit's DMA has landed (it fetched the new row's slot while that still held stale bytes): put the new row's
+      // codes and scales over it, in front of the unit's first read.  LDS operations of a wave execute in order.
+      if (jw == own_jw) {
+        const int r = L_old - row0;
+        const uint32_t ca = sl + nr_v * KV_BYTES + r * D + ((nr_dl ^ ((r / RPWIN) & (CPR - 1))) * 16);
+        const uint32_t sa = sl + 2 * KV_BYTES + nr_v * 128 + 4 * r;
+        if (nr_lane) {
+          asm volatile("ds_write_b128 %0, %1" ::"v"(ca), "v"(__builtin_bit_cast(u32x4_t, nr_codes)) : "memory");
+          if (nr_dl == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(sa), "v"(nr_scale) : "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }
+    }
 
     // ---- logits of 2 x 16 rows ----------------------------------------------------------------------------------------
     u32x4_t kd[2][KCH], ks4[2], vs4[2];
@@ -580,6 +648,8 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
     if (g == 0) *reinterpret_cast<float2*>(ring + ST_ML + j * 8) = make_float2(m_run, l_run);
   }
   __syncthreads();
+  if constexpr (APPEND)
+    if (S == 1 && tid == 0) seq_lens[lidx] = L_old + 1;  // one workgroup per (b, h); every wave read L_old before the barrier
   for (int idx = tid; idx < G * D; idx += NW * 64) {
     const int hd = idx / D, d = idx % D;
     float2 ml[NW];
@@ -604,23 +674,36 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
       if (d == 0) pl[hd] = M + __logf(den);
     }
   }
+  if constexpr (APPEND) {
+    // The owning wave writes the new row to the paged cache: last, so that nothing above waits for these stores.
+    if (own_jw >= 0 && nr_lane) {
+      *reinterpret_cast<uint4*>((nr_v ? vc : kc) + own_prow * D + nr_dl * 16) = nr_codes;
+      if (nr_dl == 0) (nr_v ? vsc : ksc)[own_prow] = nr_scale;
+    }
+  }
 }
 
+// nr == nullptr: attention over the gathered lengths; otherwise the fused append on the layer's length table
 template <typename T, int D>
-static int launch_decode_fp8(const void* q, const void* kc, const void* vc, const float* ksc, const float* vsc, void* out,
-                             const int* seq_lens, const int* page_table, const int* bmap, char* ws, int B, int HQ,
-                             int HKV, int PS, int NLP, float scale, int S, hipStream_t st) {
+static int launch_decode_fp8(const void* q, void* kc, void* vc, float* ksc, float* vsc, void* out, int* seq_lens,
+                             const int* page_table, const int* bmap, char* ws, int B, int HQ, int HKV, int PS, int NLP,
+                             float scale, int S, hipStream_t st, const Fp8NewRow* nr) {
   constexpr int R = D == 128 ? 4 : 6;
   constexpr size_t smem = fp8_ring_bytes<D, R>();
   static_assert(smem <= 160 * 1024, "LDS budget");
-  auto kern = decode_fp8_kernel<T, D, R>;
-  set_dyn_lds_once(kern, (int)smem);
   float* part_o = S > 1 ? reinterpret_cast<float*>(ws + DEC_WS_HEADER) : nullptr;
   float* part_lse = S > 1 ? part_o + (size_t)B * S * HQ * D : nullptr;
-  hipLaunchKernelGGL(kern, dim3(B * HKV * S), dim3(F8_NW * 64), smem, st, (const uint16_t*)q, (const uint8_t*)kc,
-                     (const uint8_t*)vc, ksc, vsc, seq_lens, page_table, bmap, (uint16_t*)out, part_o, part_lse, HKV,
-                     HQ / HKV, PS, NLP, S, scale);
-  if (S > 1) return launch_decode_stage2(part_o, part_lse, out, B, HQ, D, S, T::code, st);
+  auto launch = [&](auto kern, const Fp8NewRow& row) {
+    set_dyn_lds_once(kern, (int)smem);
+    hipLaunchKernelGGL(kern, dim3(B * HKV * S), dim3(F8_NW * 64), smem, st, (const uint16_t*)q, (uint8_t*)kc,
+                       (uint8_t*)vc, ksc, vsc, seq_lens, page_table, bmap, (uint16_t*)out, part_o, part_lse, HKV,
+                       HQ / HKV, PS, NLP, S, scale, row);
+  };
+  if (nr) launch(decode_fp8_kernel<T, D, R, true>, *nr);
+  else launch(decode_fp8_kernel<T, D, R, false>, Fp8NewRow{});
+  if (S > 1)  // with an appended row the merge kernel publishes L_old + 1: every stage-1 reader of L_old is done by then
+    return launch_decode_stage2(part_o, part_lse, out, B, HQ, D, S, T::code, st, nr ? seq_lens : nullptr, bmap,
+                                HQ / HKV, nr ? nr->reserved : -1);
   return check_launch();
 }
 
@@ -755,9 +838,40 @@ extern "C" int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const v
     return CVLLM_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_TD(dtype, D, {
-    return (launch_decode_fp8<TT, DD>(q, k_cache, v_cache, k_scale, v_scale, out, seq_lens_bh, page_table,
+    // without an appended row the kernel only reads the caches, the scales and the lengths
+    return (launch_decode_fp8<TT, DD>(q, (void*)k_cache, (void*)v_cache, (float*)k_scale, (float*)v_scale, out,
+                                      (int*)seq_lens_bh, page_table, batch_mapping, (char*)workspace, B, HQ, HKV,
+                                      page_size, n_logical_pages_max, sm_scale, n_splits, st, nullptr));
+  });
+  return CVLLM_ERR_SHAPE;
+}
+
+// The fused decode step on an FP8 cache: quantise and append the new K/V row of every (b,h) at
+// bh_seq_lens[batch_mapping[b], h] (RESERVED rows skipped), attend over the rows including it, publish the new lengths.
+extern "C" int cvllm_decode_append_attn_fp8(const void* q, const void* key, const void* value, int64_t sk_b,
+                                            int64_t sk_h, int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache,
+                                            void* out, int32_t* bh_seq_lens, const int32_t* page_table,
+                                            const int32_t* batch_mapping, void* workspace, size_t workspace_bytes,
+                                            int B, int HQ, int HKV, int D, int page_size, int n_logical_pages_max,
+                                            float sm_scale, int n_splits, int reserved_batch, int dtype,
+                                            cvllm_stream_t stream, float* k_scale, float* v_scale) {
+  if (!q || !key || !value || !k_cache || !v_cache || !out || !bh_seq_lens || !page_table || !batch_mapping ||
+      !k_scale || !v_scale)
+    return CVLLM_ERR_ARG;
+  if (B <= 0 || HQ <= 0 || HKV <= 0 || n_splits <= 0 || n_logical_pages_max <= 0) return CVLLM_ERR_ARG;
+  if (HQ % HKV != 0 || n_splits > 256) return CVLLM_ERR_SHAPE;
+  const int G = HQ / HKV;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return CVLLM_ERR_SHAPE;
+  if (page_size <= 0 || page_size % F8_UR != 0) return CVLLM_ERR_SHAPE;
+  if ((sk_b % 8) || (sk_h % 8) || (sv_b % 8) || (sv_h % 8)) return CVLLM_ERR_SHAPE;  // 16 B source loads
+  if (n_splits > 1 && (!workspace || workspace_bytes < cvllm_decode_workspace_bytes(B, HQ, D, n_splits)))
+    return CVLLM_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const Fp8NewRow nr{(const uint16_t*)key, (const uint16_t*)value, sk_b, sk_h, sv_b, sv_h, reserved_batch};
+  DISPATCH_TD(dtype, D, {
+    return (launch_decode_fp8<TT, DD>(q, k_cache, v_cache, k_scale, v_scale, out, bh_seq_lens, page_table,
                                       batch_mapping, (char*)workspace, B, HQ, HKV, page_size, n_logical_pages_max,
-                                      sm_scale, n_splits, st));
+                                      sm_scale, n_splits, st, &nr));
   });
   return CVLLM_ERR_SHAPE;
 }

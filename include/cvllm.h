@@ -321,12 +321,24 @@ int cvllm_compact_store_fp8(const void* new_keys, const void* new_vals, int64_t 
  * n_splits and the workspace as cvllm_decode_attn (cvllm_decode_workspace_bytes; zero when handed over, zero again
  * afterwards).  D in {64, 128}, G in {1, 2, 4, 8}, page_size % 32 == 0, any n_logical_pages_max.  Splits are always
  * merged by the second kernel (fp32 partials + LSE); rows with L == 0 produce zeros.  The grid depends on the integer
- * arguments only: capture safe.  No fused append and no LSE output.                                             */
+ * arguments only: capture safe.  No LSE output.                                                                 */
 int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
                           const float* v_scale, void* out, const int32_t* seq_lens_bh, const int32_t* page_table,
                           const int32_t* batch_mapping, void* workspace, size_t workspace_bytes, int B, int HQ,
                           int HKV, int D, int page_size, int n_logical_pages_max, float sm_scale, int n_splits,
                           int dtype, cvllm_stream_t stream);
+/* The fused decode step on an FP8 cache: cvllm_decode_append_attn's argument list and contract plus the two scale
+ * arrays.  The new K/V row of every (b,h) (key / value [B,HKV,D] in `dtype`, strides multiples of 8 elements) is
+ * quantised as cvllm_store_decode_kv_fp8 quantises it, written at bh_seq_lens[batch_mapping[b], h] and attended to in
+ * the same launch; codes, scales, lengths and outputs equal cvllm_store_decode_kv_fp8 followed by cvllm_decode_attn_fp8
+ * with the same n_splits bit for bit.  Shapes and workspace as cvllm_decode_attn_fp8; capture safe.              */
+int cvllm_decode_append_attn_fp8(const void* q, const void* key, const void* value, int64_t sk_b, int64_t sk_h,
+                                 int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache, void* out,
+                                 int32_t* bh_seq_lens, const int32_t* page_table, const int32_t* batch_mapping,
+                                 void* workspace, size_t workspace_bytes, int B, int HQ, int HKV, int D,
+                                 int page_size, int n_logical_pages_max, float sm_scale, int n_splits,
+                                 int reserved_batch, int dtype, cvllm_stream_t stream, float* k_scale,
+                                 float* v_scale);
 /* FP8 cache, in-place compaction: cvllm_compact_cache_inplace on e4m3 codes.  A kept row's D bytes of codes and its
  * two scales move together, nothing is re-quantised: the same bits as cvllm_compact_store_fp8 fed with the packed
  * 16-bit rows.  D in {64, 128}. */

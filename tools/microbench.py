@@ -1,6 +1,7 @@
 """Kernel micro-benchmarks on one MI355X (HIP-event timed on the launch stream).
 
     python tools/microbench.py decode [--L 16384] [--B 1] [--splits 0]
+    python tools/microbench.py decode --step [--kv-dtype fp8] [--L 16640] [--B 1]
 """
 import argparse
 import math
@@ -82,6 +83,69 @@ def bench_decode(args):
             us = time_fn(g.replay, iters=50, warmup=max(3, int(40e3 / (25.0 * layers)))) / layers  # ~40 ms of warm replays: settled clocks
             print(f"decode{' kv=fp8' if fp8 else ''} variant={variant} B={B} L={L} splits={S:3d} layers={layers}: {us:8.2f} us/(stage1+merge)  "
                   f"{bytes_alg / us / 1e6:7.3f} TB/s algorithmic", flush=True)
+
+
+def bench_decode_step(args):
+    """`decode --step`: the period of one whole decode-layer step (append the token's K/V row, attend, publish the
+    lengths) under graph replay, `layers` steps over distinct caches per graph: the four-call sequence (index_select,
+    decode_store_kv, attention, index_copy_) - timed twice, the difference is the run-to-run spread - and
+    fused_decode_step.  Splits as planned by default.  Every replay appends a row, so the caches have slack pages and
+    every leg starts from the same lengths."""
+    import compactor_vllm_amd.attention.sparse_decode_kernel as dk
+    from compactor_vllm_amd.kv_cache.store_kv_cache import decode_store_kv
+
+    dev = torch.device("cuda:0")
+    dtype = torch.bfloat16
+    B, HQ, HKV, D, PS, L = args.B, 32, 8, 128, 128, args.L
+    slack = 4096  # rows a leg may append: warm replays + timed replays
+    layers = max(1, min(32, int(600e6 // (2 * B * HKV * L * D * 2)) + 1))
+    caches, pt, bm, _ = build_cache(B, HKV, D, PS, L + slack, dtype, dev, layers)
+    fp8 = args.kv_dtype == "fp8"
+    scales = [{}] * layers
+    if fp8:
+        caches = [(kc.to(torch.float8_e4m3fn), vc.to(torch.float8_e4m3fn)) for kc, vc in caches]
+        scales = [dict(k_scale=torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005,
+                       v_scale=torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005) for kc, _ in caches]
+    tables = [torch.zeros(B + 1, HKV, dtype=torch.int32, device=dev) for _ in range(layers)]
+    bm_long = bm.long()
+    qkv = torch.randn(B, HQ + 2 * HKV, D, device=dev, dtype=dtype)  # key / value: views of the fused projection
+    q, k, v = qkv[:, :HQ].contiguous(), qkv[:, HQ:HQ + HKV], qkv[:, HQ + HKV:]
+
+    def four_calls():
+        for (kc, vc), sc, table in zip(caches, scales, tables):
+            seq = table.index_select(0, bm)
+            decode_store_kv(key=k, value=v, batch_mapping=bm, bh_lens=seq, page_table=pt, k_cache=kc, v_cache=vc,
+                            PAGE_SIZE=PS, **sc)
+            dk.head_sparse_decode_attention(q, kc, vc, seq, pt, bm, HKV, PS, **sc)
+            table.index_copy_(0, bm_long, seq)
+
+    def fused():
+        for (kc, vc), sc, table in zip(caches, scales, tables):
+            dk.fused_decode_step(q, k, v, kc, vc, table, pt, bm, HKV, PS, **sc)
+
+    side = torch.cuda.Stream(dev)
+    warm = max(3, int(40e3 / (25.0 * layers)))  # ~40 ms of warm replays: settled clocks
+    iters = 200
+    assert 1 + warm + iters <= slack
+    us = {}
+    for name, step in (("four-call", four_calls), ("fused", fused), ("four-call again", four_calls)):
+        for table in tables:
+            table.fill_(L)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):  # the per-stream workspace is allocated here, not inside the capture
+            step()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            step()
+        us[name] = time_fn(g.replay, iters=iters, warmup=warm) / layers
+        assert int(tables[0][1, 0]) == L + 1 + warm + iters, "every replay must append one row"
+        print(f"decode step kv={'fp8' if fp8 else 'bf16'} B={B} L={L} layers={layers} {name:15s}: {us[name]:8.2f} us/layer",
+              flush=True)
+    spread = abs(us["four-call"] - us["four-call again"])
+    print(f"decode step kv={'fp8' if fp8 else 'bf16'} B={B} L={L}: fused - four-call = "
+          f"{us['fused'] - min(us['four-call'], us['four-call again']):+.2f} us/layer, four-call spread {spread:.2f} us",
+          flush=True)
 
 
 def bench_prefill(args):
@@ -194,10 +258,11 @@ if __name__ == "__main__":
     ap.add_argument("--kv-dtype", choices=["model", "fp8"], default="model",
                     help="decode, prefill: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
     ap.add_argument("--prefix", type=int, default=0, help="prefill: cached prefix rows per head in front of the --L appended tokens")
+    ap.add_argument("--step", action="store_true", help="decode: whole layer steps (append + attend + lengths), four-call against fused")
     ap.add_argument("--flush", action="store_true", help="decode: a 128 MB device copy between launches (cold metadata, as inside a decode step)")
     ap.add_argument("--iters", type=int, default=0)      # scoring: timed calls per item (0 = default)
     ap.add_argument("--warmup", type=int, default=-1)    # scoring: warm calls per item (-1 = default)
     ap.add_argument("--with-producer", action="store_true")  # scoring: add the f-2 producer kernel
     ap.add_argument("--only", default="")                # scoring: substring filter on the item name
     a = ap.parse_args()
-    {"decode": bench_decode, "prefill": bench_prefill, "scoring": bench_scoring}[a.what](a)
+    {"decode": bench_decode_step if a.step else bench_decode, "prefill": bench_prefill, "scoring": bench_scoring}[a.what](a)
