@@ -45,20 +45,78 @@ def _chunked_post_rope(q, k, context):
     if not ch.is_last:
         return None
     attn = ch.state.attn[li]
-    HKV, D = k.shape[1], k.shape[2]
-    k_all = torch.empty((ch.total_len, HKV, D), dtype=k.dtype, device=k.device)
-    if ch.start > 0:
-        pos = torch.arange(ch.start, device=k.device)
-        pages = attn.page_table[context.batch_mapping[0].long()].long()  # [HKV, P] of the sequence's row
-        rows = pages[:, pos // attn.page_size] * attn.page_size + (pos % attn.page_size)[None, :]  # [HKV, start]
-        if attn.k_cache.dtype == _lib.FP8:  # the prefill kernel's read-back rule: (fp32(code) * scale) rounded to k.dtype
-            codes = attn.k_cache.view(torch.uint8)[rows].view(_lib.FP8)
-            k_all[: ch.start] = (codes.float() * attn.k_scale[rows][..., None]).to(k.dtype).transpose(0, 1)
-        else:
-            k_all[: ch.start] = attn.k_cache[rows].transpose(0, 1)
-    k_all[ch.start :] = k
     cu_k = torch.tensor([0, ch.total_len], dtype=torch.int32).to(k.device, non_blocking=True)
-    return query_aware_key_scores(q, k_all, context.cu_seqlens_q, cu_k, w=32, max_seqlen_k=ch.total_len)
+    return query_aware_key_scores_paged(
+        q, k, context.cu_seqlens_q, context.cu_seqlens_k, cu_k, attn.k_cache, attn.page_table, context.batch_mapping,
+        attn.page_size, w=32, k_scale=attn.k_scale, max_seqlen_k=ch.total_len)
+
+
+def query_aware_key_scores_paged(
+    q: torch.Tensor,  # [N_q, Hq, D]
+    k: torch.Tensor,  # [N_new, Hk, D]: the keys that are not in the cache yet
+    cu_seqlens_q: torch.Tensor,  # [B+1], int32
+    cu_seqlens_new: torch.Tensor,  # [B+1], int32: rows of `k`
+    cu_seqlens_k: torch.Tensor,  # [B+1], int32: all keys, cached prefix + new
+    k_cache: torch.Tensor,  # [cache_rows, D], q.dtype or FP8 codes
+    page_table: torch.Tensor,  # [Bmax, Hk, n_logical_pages] int32
+    batch_mapping: torch.Tensor,  # [B] int32
+    PAGE_SIZE: int,
+    w: "torch.Tensor | int",
+    sm_scale: float = None,
+    *,
+    k_scale: torch.Tensor = None,  # [cache_rows] fp32, with an FP8 cache
+    max_seqlen_k: int = None,
+    pool_tile: int = 128,
+) -> torch.Tensor:
+    """`query_aware_key_scores` with the keys read in place: sequence b's keys are its first
+    P_b = L_b - L_new_b rows in the paged `k_cache` (per kv-head, through `page_table[batch_mapping[b]]`) followed by
+    its rows of `k`.  An FP8 cache is read back as (fp32(code) * k_scale[row]) rounded to q.dtype, the prefill kernel's
+    rule.  fp32 [sum L_b, Hk], bit-identical to `query_aware_key_scores` on the gathered keys; no copy of the keys is
+    made.  No host sync when `max_seqlen_k` is given, `w` is an int and B = 1 (a batch's row count sum L_b is read
+    from `cu_seqlens_k`)."""
+    assert q.stride(-1) == 1 and k.stride(-1) == 1, "last dim must be contiguous"
+    assert pool_tile in (32, 64, 128), "pool_tile must be one of the reference's BLOCK_K configurations"
+    _lib.require_cuda(q, k, cu_seqlens_q, cu_seqlens_new, cu_seqlens_k, k_cache, page_table, batch_mapping)
+    w_b = None
+    if not isinstance(w, int):
+        _lib.require_cuda(w)
+        w_b = _lib.i32(w)
+        assert w_b.numel() == cu_seqlens_q.numel() - 1
+        w = int(w_b.max().item())
+    N_q, Hq, D = q.shape
+    N_new, Hk, Dk = k.shape
+    assert (Hq % Hk) == 0, "Hq must be a multiple of Hk"
+    assert q.stride(1) == D and k.dtype == q.dtype and Dk == D
+    fp8 = k_cache.dtype == _lib.FP8
+    assert k_cache.is_contiguous() and k_cache.shape[1] == D and (fp8 or k_cache.dtype == q.dtype)
+    if fp8:
+        _lib.check_fp8_scales(k_cache, k_scale, k_scale)
+    assert page_table.dtype == torch.int32 and page_table.is_contiguous() and page_table.shape[1] == Hk
+    if sm_scale is None:
+        sm_scale = 1.0 / math.sqrt(D)
+    B = cu_seqlens_q.numel() - 1
+    assert B == cu_seqlens_k.numel() - 1 == cu_seqlens_new.numel() - 1 == batch_mapping.numel()
+    cq, cn, ck = _lib.i32(cu_seqlens_q), _lib.i32(cu_seqlens_new), _lib.i32(cu_seqlens_k)
+    bm = _lib.i32(batch_mapping)
+    if max_seqlen_k is None:
+        max_seqlen_k = int(ck.diff().max().item())
+    # rows of the result, sum L_b: the one sequence's length (the engine's call), else read from cu_seqlens_k
+    N_k = int(max_seqlen_k) if B == 1 else int(ck[-1].item())
+    if w * (Hq // Hk) == 0:
+        return torch.zeros((N_k, Hk), dtype=torch.float32, device=q.device)
+    out = torch.empty((N_k, Hk), dtype=torch.float32, device=q.device)
+    L = _lib.lib()
+    ws_bytes = L.cvllm_snapkv_workspace_bytes(B, Hk, w, int(max_seqlen_k))
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=q.device)
+    st = L.cvllm_snapkv_scores_paged(
+        q.data_ptr(), k.data_ptr(), q.stride(0), k.stride(0), k.stride(1), k_cache.data_ptr(),
+        _lib.ptr(k_scale) if fp8 else None, page_table.data_ptr(), bm.data_ptr(), out.data_ptr(),
+        cq.data_ptr(), cn.data_ptr(), ck.data_ptr(), _lib.ptr(w_b), B, Hq, Hk, D, int(w), float(sm_scale), 5,
+        int(pool_tile), int(max_seqlen_k), int(PAGE_SIZE), page_table.shape[2], int(fp8), _lib.dtype_code(q.dtype),
+        ws.data_ptr(), ws_bytes, _lib.stream(),
+    )
+    _lib.check(st, "cvllm_snapkv_scores_paged")
+    return out
 
 
 def query_aware_key_scores(

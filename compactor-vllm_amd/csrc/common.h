@@ -116,6 +116,10 @@ int launch_decode_stage2(float* part_o, float* part_lse, void* out, int B, int H
                          hipStream_t stream, int* lens_by_row = nullptr, const int* bmap = nullptr, int G = 1,
                          int reserved = -1);
 
+// scoring.hip: snapkv_lse_kernel (row-LSE reduce between SnapKV's two passes), also launched by snapkv_paged.hip
+void launch_snapkv_lse(const float* part, float* lse, const int* cu_k, int B, int HKV, int w_max, const int* w_b, int G,
+                       int ntile_max, hipStream_t st);
+
 // dynamic-LDS limit of a kernel, set once per (kernel instantiation, device): the attribute lives on the device's
 // code object, so a second device in the same process needs its own call
 template <typename K>

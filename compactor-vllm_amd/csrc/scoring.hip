@@ -1305,6 +1305,13 @@ __global__ __launch_bounds__(SK_LSE_T) void snapkv_lse_kernel(const float* __res
   if (lane == 0) lse[(size_t)bg * ROWS + row] = m + __builtin_amdgcn_logf(ssum);
 }
 
+// the same launch for snapkv_paged.hip, whose two passes sit on either side of it
+void launch_snapkv_lse(const float* part, float* lse, const int* cu_k, int B, int HKV, int w_max, const int* w_b, int G,
+                       int ntile_max, hipStream_t st) {
+  hipLaunchKernelGGL(snapkv_lse_kernel, dim3(B * HKV * (SK_MAXQB * 32) / (SK_LSE_T / 64)), dim3(SK_LSE_T), 0, st, part,
+                     lse, cu_k, HKV, w_max, w_b, G, ntile_max);
+}
+
 }  // namespace cvllm
 
 using namespace cvllm;

@@ -202,6 +202,23 @@ int cvllm_snapkv_scores_wb(const void* q, const void* k, int64_t sq_n, int64_t s
                            const int32_t* window_b, int B, int HQ, int HKV, int D, int w_max, float sm_scale,
                            int pool, int pool_tile, int max_seqlen_k, int dtype, void* workspace,
                            size_t workspace_bytes, cvllm_stream_t stream);
+/* the same with the keys read in place (chunked prefill, prefill over a reused prefix): for sequence b and kv-head g,
+ * with L_b = cu_seqlens_k[b+1] - cu_seqlens_k[b] and P_b = L_b - (cu_seqlens_new[b+1] - cu_seqlens_new[b]) >= 0,
+ *   keys [0, P_b)   are rows page_table[batch_mapping[b], g, j / page_size] * page_size + j % page_size of
+ *                   k_cache[cache_rows, D] (page_table[*, HKV, n_logical_pages_max]; any page size, any P_b),
+ *   keys [P_b, L_b) are rows cu_seqlens_new[b] + j - P_b of the packed k[N_new, HKV, D] (strides sk_n, sk_h).
+ * cache_fp8 = 0: k_cache holds elements of `dtype`, k_scale is ignored.  cache_fp8 = 1: k_cache holds e4m3 codes and
+ * k_scale[cache_rows] their fp32 row scales; a cached key is read back as rne_dtype(fp32(code) * k_scale[row]), the rule
+ * of cvllm_prefill_attn_fp8.  scores[sum L_b, HKV] is laid out by cu_seqlens_k; the window is the last w rows of q
+ * before cu_seqlens_q[b+1].  Bit-identical to cvllm_snapkv_scores_wb on the gathered (read-back) keys.  A cache row at
+ * or past min(P_b, L_b - w) and a packed row at or past L_b - w are never read.  Workspace as above.             */
+int cvllm_snapkv_scores_paged(const void* q, const void* k, int64_t sq_n, int64_t sk_n, int64_t sk_h,
+                              const void* k_cache, const float* k_scale, const int32_t* page_table,
+                              const int32_t* batch_mapping, float* scores, const int32_t* cu_seqlens_q,
+                              const int32_t* cu_seqlens_new, const int32_t* cu_seqlens_k, const int32_t* window_b,
+                              int B, int HQ, int HKV, int D, int w_max, float sm_scale, int pool, int pool_tile,
+                              int max_seqlen_k, int page_size, int n_logical_pages_max, int cache_fp8, int dtype,
+                              void* workspace, size_t workspace_bytes, cvllm_stream_t stream);
 
 /* ---- a9: joint top-k selection ------------------------------------------------------------------
  * replaces compression/common.py:171-243 scores_to_retain_indices (torch.topk full sort) and the

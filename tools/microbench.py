@@ -233,6 +233,36 @@ def bench_scoring(args):
         ("select + compaction", store_top),
         ("store_all", store_all),
     ]
+    if args.prefix > 0:
+        # SnapKV on the last chunk of a chunked prefill: --L new tokens over --prefix cached rows per head
+        from compactor_vllm_amd.compression.snapkv import query_aware_key_scores_paged
+        assert B == 1, "--prefix: one sequence, as the chunked prefill runs it"
+        Pc, fp8 = args.prefix, args.kv_dtype == "fp8"
+        caches, ppt, pbm, _ = build_cache(B, HKV, D, PS, Pc, dtype, dev)
+        pkc, pks = caches[0][0] * 0.3, None
+        if fp8:
+            pkc, pks = (pkc * 30).to(torch.float8_e4m3fn), torch.rand(pkc.shape[0], device=dev) * 0.01 + 0.005
+        cu_all = torch.tensor([0, Pc + L], dtype=torch.int32, device=dev)
+
+        def gather_plain():  # what the hook did before the paged kernel: torch gather (+ dequantise) + the plain kernel
+            k_all = torch.empty((Pc + L, HKV, D), dtype=dtype, device=dev)
+            pos = torch.arange(Pc, device=dev)
+            rows = ppt[pbm[0].long()].long()[:, pos // PS] * PS + (pos % PS)[None, :]
+            if fp8:
+                codes = pkc.view(torch.uint8)[rows].view(torch.float8_e4m3fn)
+                k_all[:Pc] = (codes.float() * pks[rows][..., None]).to(dtype).transpose(0, 1)
+            else:
+                k_all[:Pc] = pkc[rows].transpose(0, 1)
+            k_all[Pc:] = k
+            return query_aware_key_scores(q, k_all, cu, cu_all, w=32, max_seqlen_k=Pc + L)
+
+        e, s_ = (1, 4) if fp8 else (2, 0)
+        nbytes = 2 * HKV * (Pc * (D * e + s_) + L * D * 2)  # both passes read every key once
+        tag = f"prefix={Pc} kv={'fp8' if fp8 else 'bf16'} ({nbytes / 1e6:.1f} MB algorithmic)"
+        items += [(f"snapkv gather + plain, {tag}", gather_plain),
+                  (f"snapkv paged, {tag}", lambda: query_aware_key_scores_paged(
+                      q, k, cu, cu, cu_all, pkc, ppt, pbm, PS, 32, k_scale=pks, max_seqlen_k=Pc + L)),
+                  (f"snapkv gather + plain (repeat), {tag}", gather_plain)]
     if args.with_producer:
         from compactor_vllm_amd.layers.rotary_embedding import fused_qkv_rope, get_rope
         rope = get_rope(D, D, max(L, 1024), 500000.0, None).to(dev)
@@ -244,7 +274,12 @@ def bench_scoring(args):
     for name, fn in items:
         # default ~30 ms of warm calls: settled clocks (3 warm calls read 5-15 % higher)
         us = time_fn(fn, iters=args.iters or 50, warmup=args.warmup if args.warmup >= 0 else 300)
-        print(f"scoring B={B} L={L}: {name:42s} {us:9.1f} us", flush=True)
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        print(f"scoring B={B} L={L}: {name:42s} {us:9.1f} us  peak temporaries {peak / 2**20:8.1f} MiB", flush=True)
 
 
 if __name__ == "__main__":
@@ -256,8 +291,8 @@ if __name__ == "__main__":
     ap.add_argument("--variant", type=int, default=-1)
     ap.add_argument("--fused-v", type=int, default=0, help="prefill: 1 = V (2 = K and V) as strided views of a fused qkv buffer")
     ap.add_argument("--kv-dtype", choices=["model", "fp8"], default="model",
-                    help="decode, prefill: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
-    ap.add_argument("--prefix", type=int, default=0, help="prefill: cached prefix rows per head in front of the --L appended tokens")
+                    help="decode, prefill, scoring --prefix: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
+    ap.add_argument("--prefix", type=int, default=0, help="prefill, scoring (SnapKV items): cached prefix rows per head in front of the --L appended tokens")
     ap.add_argument("--step", action="store_true", help="decode: whole layer steps (append + attend + lengths), four-call against fused")
     ap.add_argument("--flush", action="store_true", help="decode: a 128 MB device copy between launches (cold metadata, as inside a decode step)")
     ap.add_argument("--iters", type=int, default=0)      # scoring: timed calls per item (0 = default)
