@@ -28,6 +28,8 @@ SIGNATURES = {
     "cvllm_decode_merge_shards": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cvllm_decode_append_attn": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I,
                                       _I, _F, _I, _I, _I, _P]),
+    "cvllm_decode_append_attn_lse": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I,
+                                          _I, _I, _F, _I, _I, _I, _P]),
     "cvllm_decode_merge_status": (_I, [_P, _P]),
     "cvllm_decode_set_merge_mode": (_I, [_I]),
     "cvllm_num_splits": (_I, [_I, _I, _I, _I]),
@@ -65,6 +67,11 @@ SIGNATURES = {
     "cvllm_decode_attn_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "cvllm_decode_append_attn_fp8": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I,
                                           _I, _F, _I, _I, _I, _P, _P, _P]),
+    # split-KV shards on an FP8 cache: the siblings' lists with lse_out after out
+    "cvllm_decode_attn_lse_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _F, _I, _I,
+                                       _P]),
+    "cvllm_decode_append_attn_lse_fp8": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
+                                              _I, _I, _I, _F, _I, _I, _I, _P, _P, _P]),
     "cvllm_compact_cache_inplace_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cvllm_prefill_attn_fp8": (_I, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
                                     _I, _I, _I, _F, _I, _P, _P, _P]),

@@ -5,13 +5,16 @@ communication): the rows of every (layer, kv-head) of a sequence are partitioned
 each rank keeping its slice in its own `PagedKVCache` with its own per-head lengths.  A decode step is then
 
     every rank:  (out_r, lse_r) = head_sparse_decode_attention(q, its slice, return_lse=True)     # HBM-bound, local
+                 (the append rank: fused_decode_step(..., return_lse=True) - store, attend and LSE in one launch)
     all ranks:   ONE all-gather of the packed (out_r | lse_r) record: B*HQ*(2D + 4) bytes per rank and layer (8.3 KB
                  at B = 1, HQ = 32, D = 128) - RCCL over xGMI; latency-, not bandwidth-bound at this size
     every rank:  out = sum_r exp(lse_r - max) out_r / sum_r exp(lse_r - max)                         # merge kernel
 
 which is the math of the reference's split-K stage 2 (`attention/sparse_decode_kernel.py:391-435`) with the split axis
 moved across devices.  `q` is replicated (it is B*HQ*D values); the new token's K/V row is appended by ONE rank per
-step (`append_rank`), so the slices stay balanced when the caller rotates it.
+step (`append_rank`), so the slices stay balanced when the caller rotates it.  The slices may be 16-bit or FP8
+(e4m3 codes + per-row scales, `k_scale=` / `v_scale=`): shard outputs are in the model dtype either way, so the record
+and the merge are the same.
 """
 from __future__ import annotations
 
@@ -53,12 +56,14 @@ def unpack_records(buf: torch.Tensor, W: int, B: int, HQ: int, D: int, dtype: to
 def split_kv_decode_attention(q, k_cache, v_cache, seq_lens_bh, page_table, batch_mapping, HKV: int, PAGE_SIZE: int,
                               group=None, sm_scale: Optional[float] = None, *, key: Optional[torch.Tensor] = None,
                               value: Optional[torch.Tensor] = None, bh_seq_lens_layer: Optional[torch.Tensor] = None,
+                              k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
                               local_attention=None, merge=None) -> torch.Tensor:
     """One decode step of a sequence whose KV rows are split over the ranks of `group`.
 
     This rank's slice: (k_cache, v_cache, page_table, batch_mapping) with lengths `seq_lens_bh` [B, HKV] - or, when
     `key` / `value` / `bh_seq_lens_layer` are given, this rank is the step's append rank: the new row goes into its
-    slice first (fused append on the layer's [Bmax+1, HKV] table, like `Attention.forward`).
+    slice in the same launch that attends (fused append on the layer's [Bmax+1, HKV] table, like `Attention.forward`).
+    An FP8 (float8_e4m3fn) slice comes with its `k_scale` / `v_scale` [cache_rows] fp32.
     `local_attention` / `merge` exist for the CPU protocol test (gloo): they replace the two HIP calls."""
     import torch.distributed as dist
 
@@ -67,19 +72,13 @@ def split_kv_decode_attention(q, k_cache, v_cache, seq_lens_bh, page_table, batc
     if local_attention is not None:
         out, lse = local_attention(q)
     elif key is not None:
-        # append + attend, then read the LSE with a second, attention-only pass over the (now longer) slice would cost a
-        # second sweep; instead store first, then ONE attention call that also returns the LSE
-        from ..kv_cache.store_kv_cache import decode_store_kv
-
-        lens = bh_seq_lens_layer.index_select(0, batch_mapping.long()).contiguous()
-        decode_store_kv(key=key, value=value, batch_mapping=batch_mapping, bh_lens=lens, page_table=page_table,
-                        k_cache=k_cache, v_cache=v_cache, PAGE_SIZE=PAGE_SIZE)
-        bh_seq_lens_layer.index_copy_(0, batch_mapping.long(), lens)
-        out, lse = head_sparse_decode_attention(q, k_cache, v_cache, lens, page_table, batch_mapping, HKV, PAGE_SIZE,
-                                                sm_scale, return_lse=True)
+        # the append rank: store + attend + LSE + length write-back in ONE launch, on either cache type
+        out, lse = fused_decode_step(q, key, value, k_cache, v_cache, bh_seq_lens_layer, page_table, batch_mapping,
+                                     HKV, PAGE_SIZE, sm_scale, return_lse=True, k_scale=k_scale, v_scale=v_scale)
     else:
         out, lse = head_sparse_decode_attention(q, k_cache, v_cache, seq_lens_bh, page_table, batch_mapping, HKV,
-                                                PAGE_SIZE, sm_scale, return_lse=True)
+                                                PAGE_SIZE, sm_scale, return_lse=True, k_scale=k_scale,
+                                                v_scale=v_scale)
     rec = pack_record(out, lse)
     gathered = torch.empty((W * rec.numel(),), dtype=torch.uint8, device=rec.device)
     dist.all_gather_into_tensor(gathered, rec, group=group)

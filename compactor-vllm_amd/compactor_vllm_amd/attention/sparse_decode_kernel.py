@@ -158,7 +158,15 @@ def head_sparse_decode_attention(
         assert v.dtype == _lib.FP8
         _lib.check_fp8_scales(k, k_scale, v_scale)
         if return_lse:
-            raise NotImplementedError("the LSE output (split-KV shards) is not offered on an FP8 cache")
+            lse = torch.empty((B, HQ), dtype=torch.float32, device=q.device)
+            st = L.cvllm_decode_attn_lse_fp8(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), out.data_ptr(),
+                lse.data_ptr(), seq_lens_bh.data_ptr(), page_table.data_ptr(), batch_mapping.data_ptr(), _lib.ptr(ws),
+                ws_bytes, B, HQ, HKV, D, PAGE_SIZE, n_lp, float(sm_scale), n_splits, _lib.dtype_code(q.dtype),
+                _lib.stream(),
+            )
+            _lib.check(st, "cvllm_decode_attn_lse_fp8")
+            return out, lse
         st = L.cvllm_decode_attn_fp8(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), out.data_ptr(),
             seq_lens_bh.data_ptr(), page_table.data_ptr(), batch_mapping.data_ptr(), _lib.ptr(ws), ws_bytes, B, HQ,
@@ -200,12 +208,15 @@ def fused_decode_step(
     reserved_batch: int = 0,
     max_len_hint: int = 0,
     *,
+    return_lse: bool = False,
     k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
     v_scale: torch.Tensor | None = None,
 ):
     """decode_store_kv + head_sparse_decode_attention + length write-back of the reference's decode branch
     (layers/attention.py:127-160) in one C-ABI call that works directly on the layer's length table.  On an FP8 cache
-    the new row is quantised in the attention kernel (csrc/kv_fp8.hip): the same bits as the separate calls."""
+    the new row is quantised in the attention kernel (csrc/kv_fp8.hip): the same bits as the separate calls.
+    `return_lse=True` returns (out, lse [B, HQ] fp32) with the LSE over the rows including the new one (-inf on a
+    RESERVED row): the append rank's step of attention/cross_gpu_decode.py, still one launch."""
     _lib.require_cuda(q, key, value, k_cache, v_cache, bh_seq_lens_layer, page_table, batch_mapping)
     fp8 = k_cache.dtype == _lib.FP8
     if fp8:
@@ -230,18 +241,20 @@ def fused_decode_step(
     if n_splits > 1:
         ws_bytes = L.cvllm_decode_workspace_bytes(B, HQ, D, n_splits)
         ws = _workspace(q.device, ws_bytes)
+    lse = torch.empty((B, HQ), dtype=torch.float32, device=q.device) if return_lse else None
     args = (
         q.data_ptr(), key.data_ptr(), value.data_ptr(), key.stride(0), key.stride(1), value.stride(0), value.stride(1),
-        k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), bh_seq_lens_layer.data_ptr(), page_table.data_ptr(),
+        k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), *((lse.data_ptr(),) if return_lse else ()),
+        bh_seq_lens_layer.data_ptr(), page_table.data_ptr(),
         batch_mapping.data_ptr(), _lib.ptr(ws), ws_bytes, B, HQ, HKV, D, PAGE_SIZE, n_lp, float(sm_scale), n_splits,
         int(reserved_batch), _lib.dtype_code(q.dtype), _lib.stream(),
     )
+    name = "cvllm_decode_append_attn" + ("_lse" if return_lse else "") + ("_fp8" if fp8 else "")
     if fp8:
-        _lib.check(L.cvllm_decode_append_attn_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr()),
-                   "cvllm_decode_append_attn_fp8")
+        _lib.check(getattr(L, name)(*args, k_scale.data_ptr(), v_scale.data_ptr()), name)
     else:
-        _lib.check(L.cvllm_decode_append_attn(*args), "cvllm_decode_append_attn")
-    return out
+        _lib.check(getattr(L, name)(*args), name)
+    return (out, lse) if return_lse else out
 
 
 @functools.lru_cache(maxsize=128)

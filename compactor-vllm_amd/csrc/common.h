@@ -110,11 +110,12 @@ int store_decode_kv_impl(const void* key, const void* value, int64_t sk_b, int64
 // and zero); behind it the two-kernel path keeps part_o[B,S,HQ,D] then part_lse[B,S,HQ] (fp32).  launch_decode_stage2
 // merges them into out[B,HQ,D] and hands the words it read back zeroed (kv_fp8.hip's stage 1 uses it too).  With
 // lens_by_row != nullptr it also publishes the fused append: lens_by_row[bmap[b], h] += 1 for every (b, kv-head) whose
-// row is not `reserved` (the layer's [Bmax+1, HQ/G] table).
+// row is not `reserved` (the layer's [Bmax+1, HQ/G] table).  With lse_out != nullptr it also writes lse_out[B,HQ], the
+// natural-log LSE over all S splits (-inf where every split was empty).
 constexpr size_t DEC_WS_HEADER = 256;
 int launch_decode_stage2(float* part_o, float* part_lse, void* out, int B, int HQ, int D, int S, int dtype,
                          hipStream_t stream, int* lens_by_row = nullptr, const int* bmap = nullptr, int G = 1,
-                         int reserved = -1);
+                         int reserved = -1, float* lse_out = nullptr);
 
 // scoring.hip: snapkv_lse_kernel (row-LSE reduce between SnapKV's two passes), also launched by snapkv_paged.hip
 void launch_snapkv_lse(const float* part, float* lse, const int* cu_k, int B, int HKV, int w_max, const int* w_b, int G,

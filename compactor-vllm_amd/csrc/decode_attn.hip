@@ -1038,16 +1038,16 @@ __global__ __launch_bounds__(256) void decode_merge_shards_kernel(const uint16_t
   *reinterpret_cast<uint4*>(out + (size_t)row * D + 8 * c) = o;
 }
 
-// stage 2 on its own (no LSE output): the merge of kv_fp8.hip's stage-1 partials; lens_by_row != nullptr: its fused
-// append, whose L_old + 1 this kernel publishes in the layer's table
+// stage 2 on its own: the merge of kv_fp8.hip's stage-1 partials; lens_by_row != nullptr: its fused append, whose
+// L_old + 1 this kernel publishes in the layer's table; lse_out != nullptr: the shard form's LSE output
 int launch_decode_stage2(float* part_o, float* part_lse, void* out, int B, int HQ, int D, int S, int dtype,
-                         hipStream_t stream, int* lens_by_row, const int* bmap, int G, int reserved) {
+                         hipStream_t stream, int* lens_by_row, const int* bmap, int G, int reserved, float* lse_out) {
   if (D != 64 && D != 128) return CVLLM_ERR_SHAPE;
   const dim3 grid(B * HQ), block(256);
   const int append = lens_by_row != nullptr ? 1 : 0;
 #define CVLLM_STAGE2(T_, D_)                                                                                          \
   hipLaunchKernelGGL((decode_stage2_kernel<T_, D_>), grid, block, 0, stream, part_o, part_lse, (uint16_t*)out, HQ, S, \
-                     lens_by_row, bmap, G, append, append, reserved, (float*)nullptr)
+                     lens_by_row, bmap, G, append, append, reserved, lse_out)
   if (dtype == CVLLM_F16) {
     if (D == 64) CVLLM_STAGE2(F16, 64); else CVLLM_STAGE2(F16, 128);
   } else if (dtype == CVLLM_BF16) {
@@ -1275,21 +1275,49 @@ extern "C" int cvllm_decode_merge_shards(const void* out_all, const float* lse_a
 // Fused decode step of the boundary orchestrator (cv/layers/attention.py:127-160 decode branch): append the new
 // K/V row of every (b,h) at bh_seq_lens[batch_mapping[b], h] (in place, RESERVED rows skipped), then attend.
 // bh_seq_lens is the LAYER's full [Bmax+1, HKV] table: no index_select / index_copy round trip on the host side.
+static int decode_append_attn(const void* q, const void* key, const void* value, int64_t sk_b, int64_t sk_h,
+                              int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache, void* out, float* lse_out,
+                              int32_t* bh_seq_lens, const int32_t* page_table, const int32_t* batch_mapping,
+                              void* workspace, size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                              int n_logical_pages_max, float sm_scale, int n_splits, int reserved_batch, int dtype,
+                              cvllm_stream_t stream) {
+  if (!key || !value) return CVLLM_ERR_ARG;
+  if ((sk_b % 8) || (sk_h % 8) || (sv_b % 8) || (sv_h % 8)) return CVLLM_ERR_SHAPE;
+  DecodeArgs a{};
+  a.q = q; a.key_new = key; a.val_new = value; a.kc = k_cache; a.vc = v_cache; a.out = out; a.lse_out = lse_out;
+  a.seq_lens = bh_seq_lens; a.page_table = page_table; a.bmap = batch_mapping; a.ws = (char*)workspace;
+  a.sk_b = sk_b; a.sk_h = sk_h; a.sv_b = sv_b; a.sv_h = sv_h;
+  a.B = B; a.HKV = HKV; a.PS = page_size; a.NLP = n_logical_pages_max; a.S = n_splits; a.lens_by_row = 1;
+  a.reserved = reserved_batch; a.scale = sm_scale; a.st = (hipStream_t)stream;
+  return decode_common(a, HQ, D, dtype, workspace_bytes);
+}
+
 extern "C" int cvllm_decode_append_attn(const void* q, const void* key, const void* value, int64_t sk_b, int64_t sk_h,
                                         int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache, void* out,
                                         int32_t* bh_seq_lens, const int32_t* page_table,
                                         const int32_t* batch_mapping, void* workspace, size_t workspace_bytes, int B,
                                         int HQ, int HKV, int D, int page_size, int n_logical_pages_max, float sm_scale,
                                         int n_splits, int reserved_batch, int dtype, cvllm_stream_t stream) {
-  if (!key || !value) return CVLLM_ERR_ARG;
-  if ((sk_b % 8) || (sk_h % 8) || (sv_b % 8) || (sv_h % 8)) return CVLLM_ERR_SHAPE;
-  DecodeArgs a{};
-  a.q = q; a.key_new = key; a.val_new = value; a.kc = k_cache; a.vc = v_cache; a.out = out;
-  a.seq_lens = bh_seq_lens; a.page_table = page_table; a.bmap = batch_mapping; a.ws = (char*)workspace;
-  a.sk_b = sk_b; a.sk_h = sk_h; a.sv_b = sv_b; a.sv_h = sv_h;
-  a.B = B; a.HKV = HKV; a.PS = page_size; a.NLP = n_logical_pages_max; a.S = n_splits; a.lens_by_row = 1;
-  a.reserved = reserved_batch; a.scale = sm_scale; a.st = (hipStream_t)stream;
-  return decode_common(a, HQ, D, dtype, workspace_bytes);
+  return decode_append_attn(q, key, value, sk_b, sk_h, sv_b, sv_h, k_cache, v_cache, out, nullptr, bh_seq_lens,
+                            page_table, batch_mapping, workspace, workspace_bytes, B, HQ, HKV, D, page_size,
+                            n_logical_pages_max, sm_scale, n_splits, reserved_batch, dtype, stream);
+}
+
+// The append rank's step of a split-KV decode: the fused step plus lse_out[B,HQ] over the rows INCLUDING the appended
+// one.  All three writers of lse_out in decode_fused_kernel / decode_stage2_kernel (one split, in-launch merge, stage 2)
+// reduce over L = L_old + 1 rows, because every split derives its row range from that L; a RESERVED row has L = 0, so
+// every split of it is empty and the LSE is -inf.
+extern "C" int cvllm_decode_append_attn_lse(const void* q, const void* key, const void* value, int64_t sk_b,
+                                            int64_t sk_h, int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache,
+                                            void* out, float* lse_out, int32_t* bh_seq_lens,
+                                            const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
+                                            size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                                            int n_logical_pages_max, float sm_scale, int n_splits, int reserved_batch,
+                                            int dtype, cvllm_stream_t stream) {
+  if (!lse_out) return CVLLM_ERR_ARG;
+  return decode_append_attn(q, key, value, sk_b, sk_h, sv_b, sv_h, k_cache, v_cache, out, lse_out, bh_seq_lens,
+                            page_table, batch_mapping, workspace, workspace_bytes, B, HQ, HKV, D, page_size,
+                            n_logical_pages_max, sm_scale, n_splits, reserved_batch, dtype, stream);
 }
 
 // Process-wide choice of the split merge for grids that fit the chip (host state, not a launch): 0 = what the

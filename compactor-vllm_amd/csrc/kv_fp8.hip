@@ -32,7 +32,10 @@
 //   * LDS image: the DMA's source addresses are permuted (16 B chunk c of row r lands at chunk c ^ swz(r)), free on the
 //     global side and conflict-free for both the 16 B row reads of K and the transposing reads of V.
 // Splits are merged by decode_stage2_kernel (decode_attn.hip) from normalised fp32 partials + LSE; one split writes
-// the output directly.  No in-launch merge.
+// the output directly.  No in-launch merge.  The shard form of a split-KV decode (cvllm_decode_attn_lse_fp8, and
+// cvllm_decode_append_attn_lse_fp8 with the fused append below) also returns the LSE of the scaled logits per query head:
+// with one split decode_fp8_kernel<.., LSE = true> writes M + log(den) from the state its output pass holds after the wave
+// merge, otherwise decode_stage2_kernel writes it from the part_lse words.
 //
 // Fused append (decode_fp8_kernel<.., APPEND = true>, cvllm_decode_append_attn_fp8): the contract of the 16-bit fused
 // append (decode_attn.hip).  The new token's row of (b, h) belongs at position L_old; every workgroup works with
@@ -355,12 +358,16 @@ struct Fp8NewRow {
 
 // APPEND: seq_lens is the layer's full [Bmax+1, HKV] table indexed by bmap[b] (lengths BEFORE the append); otherwise the
 // gathered [B, HKV] table.  The caches and scales are written with APPEND only.
-template <typename T, int D, int R, bool APPEND>
+// LSE: lse_out[B, HQ] also receives the natural-log LSE of the scaled logits over the rows this call saw (-inf for a
+// (b, head) that saw none): one shard of a split-KV decode.  With one split this kernel writes it; otherwise
+// decode_stage2_kernel does, from the part_lse words stage 1 writes anyway.  A compile-time flag, and lse_out is the
+// LAST argument: the instantiations without it keep their instruction streams.
+template <typename T, int D, int R, bool APPEND, bool LSE>
 __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
     const uint16_t* __restrict__ q, uint8_t* __restrict__ kc, uint8_t* __restrict__ vc, float* __restrict__ ksc,
     float* __restrict__ vsc, int* __restrict__ seq_lens, const int* __restrict__ page_table,
     const int* __restrict__ bmap, uint16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_lse,
-    int HKV, int G, int PS, int NLP, int S, float scale, Fp8NewRow nr) {
+    int HKV, int G, int PS, int NLP, int S, float scale, Fp8NewRow nr, float* __restrict__ lse_out) {
   constexpr int NW = F8_NW, UR = F8_UR;
   constexpr int CPR = D / 16;            // 16 B chunks per row
   constexpr int RPWIN = 256 / D;         // rows per 256 B of LDS (one pass over all banks)
@@ -406,6 +413,8 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
   if (start >= end) {  // empty split (covers L == 0): zeros / a split that weighs nothing
     if (S == 1) {
       for (int i = tid; i < G * D; i += NW * 64) out[((size_t)b * HQ + h * G) * D + i] = 0;
+      if constexpr (LSE)
+        if (tid < G) lse_out[(size_t)b * HQ + h * G + tid] = -INFINITY;  // L == 0, or a RESERVED row of the fused append
     } else if (tid < G) {
       pl[tid] = -INFINITY;
     }
@@ -669,6 +678,10 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
     const float o = num / (den * VF);
     if (S == 1) {
       out[((size_t)b * HQ + h * G + hd) * D + d] = to16<T>(o);
+      // (M, den) is head hd's state after the wave merge; the thread that owns the head's dim 0 writes M + log(den), the
+      // value the branch below hands to stage 2 (den > 0: this split has at least one valid row)
+      if constexpr (LSE)
+        if (d == 0) lse_out[(size_t)b * HQ + h * G + hd] = den > 0.f ? M + __logf(den) : -INFINITY;
     } else {  // normalised fp32 partial + natural-log LSE: what decode_stage2_kernel reads
       po[hd * D + d] = o;
       if (d == 0) pl[hd] = M + __logf(den);
@@ -683,11 +696,12 @@ __global__ __launch_bounds__(F8_NW * 64) void decode_fp8_kernel(
   }
 }
 
-// nr == nullptr: attention over the gathered lengths; otherwise the fused append on the layer's length table
+// nr == nullptr: attention over the gathered lengths; otherwise the fused append on the layer's length table.
+// lse_out != nullptr: the shard form (the LSE instantiation with one split, stage 2's LSE output otherwise)
 template <typename T, int D>
 static int launch_decode_fp8(const void* q, void* kc, void* vc, float* ksc, float* vsc, void* out, int* seq_lens,
                              const int* page_table, const int* bmap, char* ws, int B, int HQ, int HKV, int PS, int NLP,
-                             float scale, int S, hipStream_t st, const Fp8NewRow* nr) {
+                             float scale, int S, hipStream_t st, const Fp8NewRow* nr, float* lse_out) {
   constexpr int R = D == 128 ? 4 : 6;
   constexpr size_t smem = fp8_ring_bytes<D, R>();
   static_assert(smem <= 160 * 1024, "LDS budget");
@@ -697,13 +711,19 @@ static int launch_decode_fp8(const void* q, void* kc, void* vc, float* ksc, floa
     set_dyn_lds_once(kern, (int)smem);
     hipLaunchKernelGGL(kern, dim3(B * HKV * S), dim3(F8_NW * 64), smem, st, (const uint16_t*)q, (uint8_t*)kc,
                        (uint8_t*)vc, ksc, vsc, seq_lens, page_table, bmap, (uint16_t*)out, part_o, part_lse, HKV,
-                       HQ / HKV, PS, NLP, S, scale, row);
+                       HQ / HKV, PS, NLP, S, scale, row, lse_out);
   };
-  if (nr) launch(decode_fp8_kernel<T, D, R, true>, *nr);
-  else launch(decode_fp8_kernel<T, D, R, false>, Fp8NewRow{});
+  const bool lse1 = lse_out != nullptr && S == 1;  // several splits: stage 1 is the plain kernel, stage 2 writes the LSE
+  if (nr) {
+    if (lse1) launch(decode_fp8_kernel<T, D, R, true, true>, *nr);
+    else launch(decode_fp8_kernel<T, D, R, true, false>, *nr);
+  } else {
+    if (lse1) launch(decode_fp8_kernel<T, D, R, false, true>, Fp8NewRow{});
+    else launch(decode_fp8_kernel<T, D, R, false, false>, Fp8NewRow{});
+  }
   if (S > 1)  // with an appended row the merge kernel publishes L_old + 1: every stage-1 reader of L_old is done by then
     return launch_decode_stage2(part_o, part_lse, out, B, HQ, D, S, T::code, st, nr ? seq_lens : nullptr, bmap,
-                                HQ / HKV, nr ? nr->reserved : -1);
+                                HQ / HKV, nr ? nr->reserved : -1, lse_out);
   return check_launch();
 }
 
@@ -821,12 +841,12 @@ extern "C" int cvllm_compact_cache_inplace_fp8(const int32_t* kept_idx, const in
   return check_launch();
 }
 
-extern "C" int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
-                                     const float* v_scale, void* out, const int32_t* seq_lens_bh,
-                                     const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
-                                     size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
-                                     int n_logical_pages_max, float sm_scale, int n_splits, int dtype,
-                                     cvllm_stream_t stream) {
+// cvllm_decode_attn_fp8 (lse_out == nullptr) and cvllm_decode_attn_lse_fp8
+static int decode_attn_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
+                           const float* v_scale, void* out, float* lse_out, const int32_t* seq_lens_bh,
+                           const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
+                           size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                           int n_logical_pages_max, float sm_scale, int n_splits, int dtype, cvllm_stream_t stream) {
   if (!q || !k_cache || !v_cache || !k_scale || !v_scale || !out || !seq_lens_bh || !page_table || !batch_mapping)
     return CVLLM_ERR_ARG;
   if (B <= 0 || HQ <= 0 || HKV <= 0 || n_splits <= 0 || n_logical_pages_max <= 0) return CVLLM_ERR_ARG;
@@ -841,20 +861,43 @@ extern "C" int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const v
     // without an appended row the kernel only reads the caches, the scales and the lengths
     return (launch_decode_fp8<TT, DD>(q, (void*)k_cache, (void*)v_cache, (float*)k_scale, (float*)v_scale, out,
                                       (int*)seq_lens_bh, page_table, batch_mapping, (char*)workspace, B, HQ, HKV,
-                                      page_size, n_logical_pages_max, sm_scale, n_splits, st, nullptr));
+                                      page_size, n_logical_pages_max, sm_scale, n_splits, st, nullptr, lse_out));
   });
   return CVLLM_ERR_SHAPE;
 }
 
-// The fused decode step on an FP8 cache: quantise and append the new K/V row of every (b,h) at
-// bh_seq_lens[batch_mapping[b], h] (RESERVED rows skipped), attend over the rows including it, publish the new lengths.
-extern "C" int cvllm_decode_append_attn_fp8(const void* q, const void* key, const void* value, int64_t sk_b,
-                                            int64_t sk_h, int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache,
-                                            void* out, int32_t* bh_seq_lens, const int32_t* page_table,
-                                            const int32_t* batch_mapping, void* workspace, size_t workspace_bytes,
-                                            int B, int HQ, int HKV, int D, int page_size, int n_logical_pages_max,
-                                            float sm_scale, int n_splits, int reserved_batch, int dtype,
-                                            cvllm_stream_t stream, float* k_scale, float* v_scale) {
+extern "C" int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
+                                     const float* v_scale, void* out, const int32_t* seq_lens_bh,
+                                     const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
+                                     size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                                     int n_logical_pages_max, float sm_scale, int n_splits, int dtype,
+                                     cvllm_stream_t stream) {
+  return decode_attn_fp8(q, k_cache, v_cache, k_scale, v_scale, out, nullptr, seq_lens_bh, page_table, batch_mapping,
+                         workspace, workspace_bytes, B, HQ, HKV, D, page_size, n_logical_pages_max, sm_scale, n_splits,
+                         dtype, stream);
+}
+
+// One shard of a split-KV decode on an FP8 cache: cvllm_decode_attn_fp8 plus lse_out[B, HQ], the natural-log LSE of the
+// scaled logits sm_scale * k_scale[row] * (q . code_row) over the rows this call saw (-inf when it saw none)
+extern "C" int cvllm_decode_attn_lse_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
+                                         const float* v_scale, void* out, float* lse_out, const int32_t* seq_lens_bh,
+                                         const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
+                                         size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                                         int n_logical_pages_max, float sm_scale, int n_splits, int dtype,
+                                         cvllm_stream_t stream) {
+  if (!lse_out) return CVLLM_ERR_ARG;
+  return decode_attn_fp8(q, k_cache, v_cache, k_scale, v_scale, out, lse_out, seq_lens_bh, page_table, batch_mapping,
+                         workspace, workspace_bytes, B, HQ, HKV, D, page_size, n_logical_pages_max, sm_scale, n_splits,
+                         dtype, stream);
+}
+
+// cvllm_decode_append_attn_fp8 (lse_out == nullptr) and cvllm_decode_append_attn_lse_fp8
+static int decode_append_attn_fp8(const void* q, const void* key, const void* value, int64_t sk_b, int64_t sk_h,
+                                  int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache, void* out, float* lse_out,
+                                  int32_t* bh_seq_lens, const int32_t* page_table, const int32_t* batch_mapping,
+                                  void* workspace, size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                                  int n_logical_pages_max, float sm_scale, int n_splits, int reserved_batch, int dtype,
+                                  cvllm_stream_t stream, float* k_scale, float* v_scale) {
   if (!q || !key || !value || !k_cache || !v_cache || !out || !bh_seq_lens || !page_table || !batch_mapping ||
       !k_scale || !v_scale)
     return CVLLM_ERR_ARG;
@@ -871,7 +914,40 @@ extern "C" int cvllm_decode_append_attn_fp8(const void* q, const void* key, cons
   DISPATCH_TD(dtype, D, {
     return (launch_decode_fp8<TT, DD>(q, k_cache, v_cache, k_scale, v_scale, out, bh_seq_lens, page_table,
                                       batch_mapping, (char*)workspace, B, HQ, HKV, page_size, n_logical_pages_max,
-                                      sm_scale, n_splits, st, &nr));
+                                      sm_scale, n_splits, st, &nr, lse_out));
   });
   return CVLLM_ERR_SHAPE;
+}
+
+// The fused decode step on an FP8 cache: quantise and append the new K/V row of every (b,h) at
+// bh_seq_lens[batch_mapping[b], h] (RESERVED rows skipped), attend over the rows including it, publish the new lengths.
+extern "C" int cvllm_decode_append_attn_fp8(const void* q, const void* key, const void* value, int64_t sk_b,
+                                            int64_t sk_h, int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache,
+                                            void* out, int32_t* bh_seq_lens, const int32_t* page_table,
+                                            const int32_t* batch_mapping, void* workspace, size_t workspace_bytes,
+                                            int B, int HQ, int HKV, int D, int page_size, int n_logical_pages_max,
+                                            float sm_scale, int n_splits, int reserved_batch, int dtype,
+                                            cvllm_stream_t stream, float* k_scale, float* v_scale) {
+  return decode_append_attn_fp8(q, key, value, sk_b, sk_h, sv_b, sv_h, k_cache, v_cache, out, nullptr, bh_seq_lens,
+                                page_table, batch_mapping, workspace, workspace_bytes, B, HQ, HKV, D, page_size,
+                                n_logical_pages_max, sm_scale, n_splits, reserved_batch, dtype, stream, k_scale,
+                                v_scale);
+}
+
+// The append rank's step of a split-KV decode on an FP8 cache: the fused step above plus lse_out[B, HQ] over the rows
+// INCLUDING the appended one (the owner wave patches it into the unit's LDS image before the unit is reduced); -inf on a
+// RESERVED row, which attends to nothing
+extern "C" int cvllm_decode_append_attn_lse_fp8(const void* q, const void* key, const void* value, int64_t sk_b,
+                                                int64_t sk_h, int64_t sv_b, int64_t sv_h, void* k_cache,
+                                                void* v_cache, void* out, float* lse_out, int32_t* bh_seq_lens,
+                                                const int32_t* page_table, const int32_t* batch_mapping,
+                                                void* workspace, size_t workspace_bytes, int B, int HQ, int HKV, int D,
+                                                int page_size, int n_logical_pages_max, float sm_scale, int n_splits,
+                                                int reserved_batch, int dtype, cvllm_stream_t stream, float* k_scale,
+                                                float* v_scale) {
+  if (!lse_out) return CVLLM_ERR_ARG;
+  return decode_append_attn_fp8(q, key, value, sk_b, sk_h, sv_b, sv_h, k_cache, v_cache, out, lse_out, bh_seq_lens,
+                                page_table, batch_mapping, workspace, workspace_bytes, B, HQ, HKV, D, page_size,
+                                n_logical_pages_max, sm_scale, n_splits, reserved_batch, dtype, stream, k_scale,
+                                v_scale);
 }

@@ -98,6 +98,16 @@ int cvllm_decode_append_attn(const void* q, const void* key, const void* value, 
                              int B, int HQ, int HKV, int D, int page_size, int n_logical_pages_max,
                              float sm_scale, int n_splits, int reserved_batch, int dtype,
                              cvllm_stream_t stream);
+/* The append rank's step of a split-KV decode (f-4) in one launch: cvllm_decode_append_attn plus lse_out[B,HQ] fp32
+ * (required) as cvllm_decode_attn_lse defines it, over the rows INCLUDING the appended one; -inf (and a zero output)
+ * for a row with batch_mapping[b] == reserved_batch.  D <= 128, as cvllm_decode_attn_lse.                    */
+int cvllm_decode_append_attn_lse(const void* q, const void* key, const void* value, int64_t sk_b,
+                                 int64_t sk_h, int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache,
+                                 void* out, float* lse_out, int32_t* bh_seq_lens, const int32_t* page_table,
+                                 const int32_t* batch_mapping, void* workspace, size_t workspace_bytes,
+                                 int B, int HQ, int HKV, int D, int page_size, int n_logical_pages_max,
+                                 float sm_scale, int n_splits, int reserved_batch, int dtype,
+                                 cvllm_stream_t stream);
 
 /* replaces attention/sparse_decode_kernel.py:169-192 num_splits_heuristic (host, same results) */
 int cvllm_num_splits(int total_mblocks, int max_seq_len, int num_sms, int max_splits);
@@ -338,12 +348,23 @@ int cvllm_compact_store_fp8(const void* new_keys, const void* new_vals, int64_t 
  * n_splits and the workspace as cvllm_decode_attn (cvllm_decode_workspace_bytes; zero when handed over, zero again
  * afterwards).  D in {64, 128}, G in {1, 2, 4, 8}, page_size % 32 == 0, any n_logical_pages_max.  Splits are always
  * merged by the second kernel (fp32 partials + LSE); rows with L == 0 produce zeros.  The grid depends on the integer
- * arguments only: capture safe.  No LSE output.                                                                 */
+ * arguments only: capture safe.  The LSE output is cvllm_decode_attn_lse_fp8.                                   */
 int cvllm_decode_attn_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
                           const float* v_scale, void* out, const int32_t* seq_lens_bh, const int32_t* page_table,
                           const int32_t* batch_mapping, void* workspace, size_t workspace_bytes, int B, int HQ,
                           int HKV, int D, int page_size, int n_logical_pages_max, float sm_scale, int n_splits,
                           int dtype, cvllm_stream_t stream);
+/* One shard of a cross-device split-KV decode on an FP8 cache (cvllm_decode_attn_lse's role): cvllm_decode_attn_fp8
+ * plus lse_out[B,HQ] fp32 (required) = natural-log LSE of the logits sm_scale * k_scale[row] * (q . code_row) over the
+ * rows this call saw, -inf when it saw none.  With one split the attention kernel writes it, otherwise the merge kernel.
+ * out is in `dtype`, so shards of either cache type are merged by cvllm_decode_merge_shards.  Shapes, workspace and
+ * capture safety as cvllm_decode_attn_fp8.                                                                        */
+int cvllm_decode_attn_lse_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
+                              const float* v_scale, void* out, float* lse_out, const int32_t* seq_lens_bh,
+                              const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
+                              size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                              int n_logical_pages_max, float sm_scale, int n_splits, int dtype,
+                              cvllm_stream_t stream);
 /* The fused decode step on an FP8 cache: cvllm_decode_append_attn's argument list and contract plus the two scale
  * arrays.  The new K/V row of every (b,h) (key / value [B,HKV,D] in `dtype`, strides multiples of 8 elements) is
  * quantised as cvllm_store_decode_kv_fp8 quantises it, written at bh_seq_lens[batch_mapping[b], h] and attended to in
@@ -356,6 +377,17 @@ int cvllm_decode_append_attn_fp8(const void* q, const void* key, const void* val
                                  int page_size, int n_logical_pages_max, float sm_scale, int n_splits,
                                  int reserved_batch, int dtype, cvllm_stream_t stream, float* k_scale,
                                  float* v_scale);
+/* The append rank's step of a split-KV decode on an FP8 cache, in one launch: cvllm_decode_append_attn_fp8 plus
+ * lse_out[B,HQ] fp32 (required), the LSE over the rows INCLUDING the appended one; -inf (and a zero output) for a row
+ * with batch_mapping[b] == reserved_batch.  Codes, scales, lengths, out and lse equal cvllm_store_decode_kv_fp8
+ * followed by cvllm_decode_attn_lse_fp8 with the same n_splits bit for bit.                                     */
+int cvllm_decode_append_attn_lse_fp8(const void* q, const void* key, const void* value, int64_t sk_b, int64_t sk_h,
+                                     int64_t sv_b, int64_t sv_h, void* k_cache, void* v_cache, void* out,
+                                     float* lse_out, int32_t* bh_seq_lens, const int32_t* page_table,
+                                     const int32_t* batch_mapping, void* workspace, size_t workspace_bytes, int B,
+                                     int HQ, int HKV, int D, int page_size, int n_logical_pages_max, float sm_scale,
+                                     int n_splits, int reserved_batch, int dtype, cvllm_stream_t stream,
+                                     float* k_scale, float* v_scale);
 /* FP8 cache, in-place compaction: cvllm_compact_cache_inplace on e4m3 codes.  A kept row's D bytes of codes and its
  * two scales move together, nothing is re-quantised: the same bits as cvllm_compact_store_fp8 fed with the packed
  * 16-bit rows.  D in {64, 128}. */

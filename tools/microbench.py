@@ -1,7 +1,7 @@
 """Kernel micro-benchmarks on one MI355X (HIP-event timed on the launch stream).
 
     python tools/microbench.py decode [--L 16384] [--B 1] [--splits 0]
-    python tools/microbench.py decode --step [--kv-dtype fp8] [--L 16640] [--B 1]
+    python tools/microbench.py decode --step [--lse] [--kv-dtype fp8] [--L 16640] [--B 1]
 """
 import argparse
 import math
@@ -89,8 +89,9 @@ def bench_decode_step(args):
     """`decode --step`: the period of one whole decode-layer step (append the token's K/V row, attend, publish the
     lengths) under graph replay, `layers` steps over distinct caches per graph: the four-call sequence (index_select,
     decode_store_kv, attention, index_copy_) - timed twice, the difference is the run-to-run spread - and
-    fused_decode_step.  Splits as planned by default.  Every replay appends a row, so the caches have slack pages and
-    every leg starts from the same lengths."""
+    fused_decode_step.  `--lse`: both legs also return the LSE, i.e. the append rank's step of a split-KV decode (the
+    four-call leg is what that rank ran before fused_decode_step had return_lse).  Splits as planned by default.  Every
+    replay appends a row, so the caches have slack pages and every leg starts from the same lengths."""
     import compactor_vllm_amd.attention.sparse_decode_kernel as dk
     from compactor_vllm_amd.kv_cache.store_kv_cache import decode_store_kv
 
@@ -116,12 +117,12 @@ def bench_decode_step(args):
             seq = table.index_select(0, bm)
             decode_store_kv(key=k, value=v, batch_mapping=bm, bh_lens=seq, page_table=pt, k_cache=kc, v_cache=vc,
                             PAGE_SIZE=PS, **sc)
-            dk.head_sparse_decode_attention(q, kc, vc, seq, pt, bm, HKV, PS, **sc)
+            dk.head_sparse_decode_attention(q, kc, vc, seq, pt, bm, HKV, PS, return_lse=args.lse, **sc)
             table.index_copy_(0, bm_long, seq)
 
     def fused():
         for (kc, vc), sc, table in zip(caches, scales, tables):
-            dk.fused_decode_step(q, k, v, kc, vc, table, pt, bm, HKV, PS, **sc)
+            dk.fused_decode_step(q, k, v, kc, vc, table, pt, bm, HKV, PS, return_lse=args.lse, **sc)
 
     side = torch.cuda.Stream(dev)
     warm = max(3, int(40e3 / (25.0 * layers)))  # ~40 ms of warm replays: settled clocks
@@ -294,6 +295,7 @@ if __name__ == "__main__":
                     help="decode, prefill, scoring --prefix: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
     ap.add_argument("--prefix", type=int, default=0, help="prefill, scoring (SnapKV items): cached prefix rows per head in front of the --L appended tokens")
     ap.add_argument("--step", action="store_true", help="decode: whole layer steps (append + attend + lengths), four-call against fused")
+    ap.add_argument("--lse", action="store_true", help="decode --step: both legs also return the LSE (the split-KV append rank's step)")
     ap.add_argument("--flush", action="store_true", help="decode: a 128 MB device copy between launches (cold metadata, as inside a decode step)")
     ap.add_argument("--iters", type=int, default=0)      # scoring: timed calls per item (0 = default)
     ap.add_argument("--warmup", type=int, default=-1)    # scoring: warm calls per item (-1 = default)
