@@ -75,6 +75,14 @@ SIGNATURES = {
     "cvllm_compact_cache_inplace_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cvllm_prefill_attn_fp8": (_I, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
                                     _I, _I, _I, _F, _I, _P, _P, _P]),
+    # MXFP4 cache: the FP8 lists, the scales being bytes
+    "cvllm_store_decode_kv_mxfp4": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P,
+                                         _P]),
+    "cvllm_store_all_kv_mxfp4": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P,
+                                      _P]),
+    "cvllm_compact_store_mxfp4": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
+                                       _I, _I, _P, _P, _P]),
+    "cvllm_decode_attn_mxfp4": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "cvllm_rank_workspace_bytes": (_Z, [_I, _I, _I]),
     "cvllm_rank_indices": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
 }
@@ -139,6 +147,18 @@ def check_fp8_scales(k_cache: torch.Tensor, k_scale, v_scale) -> None:
         assert s is not None, f"an FP8 cache needs {name}"
         assert s.dtype == torch.float32 and s.is_contiguous(), f"{name} must be contiguous float32"
         assert s.shape == (k_cache.shape[0],), f"{name} must hold one scale per cache row"
+    require_cuda(k_scale, v_scale)
+
+
+MXFP4 = torch.uint8  # element type of an MXFP4 KV cache: two e2m1 codes per byte + one e8m0 scale byte per 32 elements
+
+
+def check_mxfp4_scales(k_cache: torch.Tensor, k_scale, v_scale) -> None:
+    """The scale arrays that go with an MXFP4 cache [rows, D/2]: present, uint8, contiguous, [rows, D/32]."""
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        assert s is not None, f"an MXFP4 cache needs {name}"
+        assert s.dtype == torch.uint8 and s.is_contiguous(), f"{name} must be contiguous uint8"
+        assert s.shape == (k_cache.shape[0], k_cache.shape[1] // 16), f"{name} must hold D/32 scale bytes per cache row"
     require_cuda(k_scale, v_scale)
 
 

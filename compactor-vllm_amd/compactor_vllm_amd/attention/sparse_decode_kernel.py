@@ -108,7 +108,7 @@ def head_sparse_decode_attention(
     key_split: int = None,
     *,
     return_lse: bool = False,
-    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    k_scale: torch.Tensor | None = None,  # FP8 cache: [cache_rows] fp32; MXFP4 (uint8) cache: [cache_rows, D/32] uint8
     v_scale: torch.Tensor | None = None,
 ):
     """Same contract as the reference wrapper (sparse_decode_kernel.py:10-68).  `return_lse=True` (extension, used by
@@ -136,7 +136,9 @@ def head_sparse_decode_attention(
     assert global_page_table.shape[1] == HKV
     assert q.is_contiguous()
     assert (D & (D - 1)) == 0, "D must be a power of 2"
-    assert k.is_contiguous() and v.is_contiguous() and k.shape[1] == D and v.shape[1] == D
+    mxfp4 = k.dtype == _lib.MXFP4  # two e2m1 codes per byte: rows of D/2 bytes
+    row_width = D // 2 if mxfp4 else D
+    assert k.is_contiguous() and v.is_contiguous() and k.shape[1] == row_width and v.shape[1] == row_width
     assert global_page_table.is_contiguous()
     n_lp = global_page_table.shape[-1]
     sm_scale = 1 / math.sqrt(D) if sm_scale is None else sm_scale
@@ -173,6 +175,18 @@ def head_sparse_decode_attention(
             HKV, D, PAGE_SIZE, n_lp, float(sm_scale), n_splits, _lib.dtype_code(q.dtype), _lib.stream(),
         )
         _lib.check(st, "cvllm_decode_attn_fp8")
+        return out
+    if mxfp4:  # e2m1 codes + e8m0 block scales: the stage-1 kernel of csrc/kv_mxfp4.hip
+        assert v.dtype == _lib.MXFP4
+        _lib.check_mxfp4_scales(k, k_scale, v_scale)
+        if return_lse:
+            raise NotImplementedError("decode attention over an MXFP4 cache has no LSE output")
+        st = L.cvllm_decode_attn_mxfp4(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), out.data_ptr(),
+            seq_lens_bh.data_ptr(), page_table.data_ptr(), batch_mapping.data_ptr(), _lib.ptr(ws), ws_bytes, B, HQ,
+            HKV, D, PAGE_SIZE, n_lp, float(sm_scale), n_splits, _lib.dtype_code(q.dtype), _lib.stream(),
+        )
+        _lib.check(st, "cvllm_decode_attn_mxfp4")
         return out
     if return_lse:
         lse = torch.empty((B, HQ), dtype=torch.float32, device=q.device)
@@ -218,6 +232,9 @@ def fused_decode_step(
     `return_lse=True` returns (out, lse [B, HQ] fp32) with the LSE over the rows including the new one (-inf on a
     RESERVED row): the append rank's step of attention/cross_gpu_decode.py, still one launch."""
     _lib.require_cuda(q, key, value, k_cache, v_cache, bh_seq_lens_layer, page_table, batch_mapping)
+    if k_cache.dtype == _lib.MXFP4:
+        raise NotImplementedError("the fused decode step has no MXFP4 form: decode_store_kv, then "
+                                  "head_sparse_decode_attention")
     fp8 = k_cache.dtype == _lib.FP8
     if fp8:
         assert v_cache.dtype == _lib.FP8

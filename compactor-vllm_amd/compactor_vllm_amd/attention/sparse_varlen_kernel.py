@@ -52,7 +52,14 @@ def causal_sparse_varlen_with_cache(
     assert q.stride(1) == D, "query heads must be contiguous"
     CACHE_SIZE = k_cache.shape[0]
     assert v_cache.shape[0] == CACHE_SIZE
-    assert k_cache.shape[1] == D and v_cache.shape[1] == D
+    mxfp4 = k_cache.dtype == _lib.MXFP4
+    if mxfp4:
+        # No prefill kernel reads 4-bit rows: an MXFP4 cache has no chunked prefill and no prefix reuse, so every prefix is
+        # empty.  The 16-bit kernel runs on zero prefix lengths (a local array: it must never dereference the cache).
+        assert k_cache.shape[1] == D // 2 and v_cache.shape[1] == D // 2
+        seq_lens_bh = torch.zeros_like(seq_lens_bh)
+    else:
+        assert k_cache.shape[1] == D and v_cache.shape[1] == D
     assert PAGE_SIZE > 0 and CACHE_SIZE % PAGE_SIZE == 0
     assert k_cache.is_contiguous() and v_cache.is_contiguous() and global_page_table.is_contiguous()
     _lib.require_cuda(q, k, v, k_cache, v_cache, seq_lens_bh, global_page_table, batch_mapping, cu_seqlens_q)

@@ -114,7 +114,7 @@ def extract_and_store_top_kv(
     PAD_TO_PAGE_SIZE: bool = True,
     K_TILE: int = 16,
     padding: float = -float("inf"),
-    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    k_scale: torch.Tensor | None = None,  # FP8 cache: [cache_rows] fp32; MXFP4 (uint8) cache: [cache_rows, D/32] uint8
     v_scale: torch.Tensor | None = None,
 ):
     """scores -> retained (token, head) pairs -> paged cache, on the current stream (reference
@@ -141,6 +141,11 @@ def extract_and_store_top_kv(
         _lib.check_fp8_scales(k_cache, k_scale, v_scale)
         st = _lib.lib().cvllm_compact_store_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr())
         _lib.check(st, "cvllm_compact_store_fp8")
+    elif k_cache.dtype == _lib.MXFP4:  # a kept row is quantised block by block as the other MXFP4 stores do
+        _lib.check_mxfp4_scales(k_cache, k_scale, v_scale)
+        assert k_cache.shape[1] == D // 2 and v_cache.shape == k_cache.shape
+        st = _lib.lib().cvllm_compact_store_mxfp4(*args, k_scale.data_ptr(), v_scale.data_ptr())
+        _lib.check(st, "cvllm_compact_store_mxfp4")
     else:
         st = _lib.lib().cvllm_compact_store(*args)
         _lib.check(st, "cvllm_compact_store")

@@ -32,14 +32,16 @@ class LLMConfig:
     leverage_sketch_size: int = 48
     attention_backend: AttentionBackend = AttentionBackend.COMPACTOR_TRITON
     show_progress_bar: bool = True
-    kv_cache_dtype: str = "auto"  # "auto" = the model dtype; "fp8_e4m3" = e4m3 codes + one fp32 scale per cache row
+    # "auto" = the model dtype; "fp8_e4m3" = e4m3 codes + one fp32 scale per cache row; "mxfp4" = OCP e2m1 codes + one
+    # e8m0 scale per 32 elements (no chunked prefill, no prefix reuse)
+    kv_cache_dtype: str = "auto"
     # FP8 cache only: prefill attention reads the FP8 prefix (cvllm_prefill_attn_fp8), which turns chunked prefill and
     # prefix reuse on.  Opt-in for now; without it an FP8 cache refuses both, as before.
     fp8_prefix_reads: bool = False
 
     def __post_init__(self):
-        if self.kv_cache_dtype not in ("auto", "fp8_e4m3"):
-            raise ValueError(f"kv_cache_dtype must be 'auto' or 'fp8_e4m3', got {self.kv_cache_dtype!r}")
+        if self.kv_cache_dtype not in ("auto", "fp8_e4m3", "mxfp4"):
+            raise ValueError(f"kv_cache_dtype must be 'auto', 'fp8_e4m3' or 'mxfp4', got {self.kv_cache_dtype!r}")
         if self.path is not None and not os.path.isdir(self.path):
             raise NotADirectoryError(f"Engine config dir {self.path} does not exist")
         if self.tensor_parallel_size <= 0 or self.tensor_parallel_size > 8:

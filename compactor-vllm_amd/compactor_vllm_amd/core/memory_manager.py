@@ -51,9 +51,15 @@ class KVCacheManager:
         self.fp8_prefix_reads = self.fp8 and bool(getattr(config, "fp8_prefix_reads", False))
         if self.fp8 and not self.fp8_prefix_reads:
             self.chunked_prefill = False  # FP8 prefix reads in prefill attention are opt-in (LLMConfig.fp8_prefix_reads)
+        self.mxfp4 = getattr(config, "kv_cache_dtype", "auto") == "mxfp4"
+        if self.mxfp4:  # e2m1 codes + e8m0 block scales; no prefill kernel reads them: no chunked prefill, no prefix reuse
+            self.cache_dtype = torch.uint8
+            self.chunked_prefill = False
 
     # ---- sizing ------------------------------------------------------------------------------------------------
     def bytes_per_page_all_layers(self) -> int:
+        if self.mxfp4:  # half a byte per element + one scale byte per 32 elements
+            return self.num_layers * 2 * self.page_size * (self.head_dim // 2 + self.head_dim // 32)
         if self.fp8:  # one byte per element + one fp32 scale per row
             return self.num_layers * 2 * self.page_size * (self.head_dim + 4)
         elt = torch.empty((), dtype=self.model_dtype).element_size()

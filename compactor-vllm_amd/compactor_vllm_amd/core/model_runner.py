@@ -159,6 +159,9 @@ class ModelRunner:
         if self.kv_manager.fp8 and not self.kv_manager.fp8_prefix_reads:
             raise NotImplementedError("prefix reuse on an FP8 cache (kv_cache_dtype='fp8_e4m3') needs prefill attention "
                                       "over FP8 rows: set LLMConfig.fp8_prefix_reads=True")
+        if self.kv_manager.mxfp4:
+            raise NotImplementedError("prefix reuse on an MXFP4 cache (kv_cache_dtype='mxfp4') needs prefill attention "
+                                      "over 4-bit rows, which does not exist")
         params = batch_compression_params if batch_compression_params is not None else BatchCompressionParams()
         method, chunk = self._scoring_key(params)
         P = (len(token_ids) // PREFIX_ALIGN) * PREFIX_ALIGN

@@ -90,11 +90,18 @@ class PagedKVCache(torch.nn.Module):
         self.H_kv = int(H_kv)
         self.max_pages_per_head = max_logical_pages_per_head
         self.max_num_batches = rows
-        self.kv_cache = torch.empty((2, num_layers, num_pages * self.page_size, head_dim), dtype=dtype, device=device)
-        # FP8 cache: e4m3 codes above + one fp32 scale per physical row, K = 0 / V = 1 (same row index as the codes)
+        cache_rows = num_pages * self.page_size
+        # MXFP4 cache (dtype uint8): two e2m1 codes per byte, so a row is head_dim / 2 bytes
+        row_width = head_dim // 2 if dtype == torch.uint8 else head_dim
+        self.kv_cache = torch.empty((2, num_layers, cache_rows, row_width), dtype=dtype, device=device)
+        # FP8 cache: e4m3 codes above + one fp32 scale per physical row, K = 0 / V = 1 (same row index as the codes);
+        # MXFP4 cache: one e8m0 scale byte per 32 elements of a row
         self.kv_scale: Optional[torch.Tensor] = None
         if dtype == torch.float8_e4m3fn:
-            self.kv_scale = torch.empty((2, num_layers, num_pages * self.page_size), dtype=torch.float32, device=device)
+            self.kv_scale = torch.empty((2, num_layers, cache_rows), dtype=torch.float32, device=device)
+        elif dtype == torch.uint8:
+            assert head_dim % 32 == 0, "an MXFP4 cache needs head_dim to be a multiple of 32"
+            self.kv_scale = torch.empty((2, num_layers, cache_rows, head_dim // 32), dtype=torch.uint8, device=device)
         per_head = dict(device=device, dtype=torch.int32)
         self.page_table = torch.zeros((num_layers, rows, self.H_kv, max_logical_pages_per_head), **per_head)
         self.bh_seq_lens = torch.zeros((num_layers, rows, self.H_kv), **per_head)
@@ -157,7 +164,9 @@ class PagedKVCache(torch.nn.Module):
             pool.give_back(batch_index, pages)
             released += len(pages)
         self.bh_num_pages[:, batch_index] = keep
-        row_bytes = self.head_dim * self.kv_cache.element_size() + (4 if self.kv_scale is not None else 0)
+        row_bytes = self.kv_cache.shape[-1] * self.kv_cache.element_size()
+        if self.kv_scale is not None:  # FP8: one fp32 per row; MXFP4: head_dim / 32 bytes per row
+            row_bytes += self.kv_scale[0, 0, 0].numel() * self.kv_scale.element_size()
         return released * self.page_size * row_bytes * 2
 
     # ---- views --------------------------------------------------------------------------------------------------
@@ -167,7 +176,7 @@ class PagedKVCache(torch.nn.Module):
         return self.kv_cache[0, layer], self.kv_cache[1, layer], self.page_table[layer], self.bh_seq_lens[layer]
 
     def layer_scale_slices(self, layer: int):
-        """(k_scale, v_scale) of one layer of an FP8 cache, (None, None) otherwise."""
+        """(k_scale, v_scale) of one layer of an FP8 or MXFP4 cache, (None, None) otherwise."""
         assert 0 <= layer < self.num_layers
         if self.kv_scale is None:
             return None, None

@@ -34,7 +34,7 @@ def prefill_store_all_kv(
     batch_mapping: torch.Tensor,  # [B] int32 (local->true)
     PAGE_SIZE: int,
     K_TILE: int = 32,  # accepted for signature parity; the HIP kernel tiles by rows per wave
-    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    k_scale: torch.Tensor | None = None,  # FP8 cache: [cache_rows] fp32; MXFP4 (uint8) cache: [cache_rows, D/32] uint8
     v_scale: torch.Tensor | None = None,
 ):
     assert new_keys.stride(-1) == 1 and new_values.stride(-1) == 1, "last dim must be contiguous"
@@ -56,6 +56,17 @@ def prefill_store_all_kv(
         )
         _lib.check(st, "cvllm_store_all_kv_fp8")
         return
+    if k_cache.dtype == _lib.MXFP4:  # quantising store: two e2m1 codes per byte + one e8m0 scale per 32 elements
+        _lib.check_mxfp4_scales(k_cache, k_scale, v_scale)
+        assert k_cache.shape[1] == D // 2 and v_cache.shape == k_cache.shape
+        st = _lib.lib().cvllm_store_all_kv_mxfp4(
+            new_keys.data_ptr(), new_values.data_ptr(), sk_n, sk_h, sv_n, sv_h, cu.data_ptr(),
+            bm.data_ptr(), bh_lens.data_ptr(), page_table.data_ptr(), k_cache.data_ptr(),
+            v_cache.data_ptr(), B, N, HKV, D, PAGE_SIZE, page_table.shape[-1], _lib.dtype_code(new_keys.dtype),
+            _lib.stream(), k_scale.data_ptr(), v_scale.data_ptr(),
+        )
+        _lib.check(st, "cvllm_store_all_kv_mxfp4")
+        return
     st = _lib.lib().cvllm_store_all_kv(
         new_keys.data_ptr(), new_values.data_ptr(), sk_n, sk_h, sv_n, sv_h, cu.data_ptr(),
         bm.data_ptr(), bh_lens.data_ptr(), page_table.data_ptr(), k_cache.data_ptr(),
@@ -76,7 +87,7 @@ def decode_store_kv(
     v_cache: torch.Tensor,  # [N_PAGES*PAGE_SIZE, D]
     PAGE_SIZE: int,
     TRITON_RESERVED_BATCH: int = None,
-    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    k_scale: torch.Tensor | None = None,  # FP8 cache: [cache_rows] fp32; MXFP4 (uint8) cache: [cache_rows, D/32] uint8
     v_scale: torch.Tensor | None = None,
 ):
     assert key.shape == value.shape and key.ndim == 3, "key/value must be [B, HKV, D]"
@@ -97,6 +108,17 @@ def decode_store_kv(
             v_scale.data_ptr(),
         )
         _lib.check(st, "cvllm_store_decode_kv_fp8")
+        return
+    if k_cache.dtype == _lib.MXFP4:
+        _lib.check_mxfp4_scales(k_cache, k_scale, v_scale)
+        assert k_cache.shape[1] == D // 2 and v_cache.shape == k_cache.shape
+        st = _lib.lib().cvllm_store_decode_kv_mxfp4(
+            key.data_ptr(), value.data_ptr(), sk_b, sk_h, sv_b, sv_h, batch_mapping.data_ptr(), bh_lens.data_ptr(),
+            page_table.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), int(batch_mapping.shape[0]), HKV, D,
+            PAGE_SIZE, page_table.shape[2], reserved, _lib.dtype_code(key.dtype), _lib.stream(), k_scale.data_ptr(),
+            v_scale.data_ptr(),
+        )
+        _lib.check(st, "cvllm_store_decode_kv_mxfp4")
         return
     st = _lib.lib().cvllm_store_decode_kv(
         key.data_ptr(), value.data_ptr(), sk_b, sk_h, sv_b, sv_h, batch_mapping.data_ptr(), bh_lens.data_ptr(),
@@ -126,8 +148,8 @@ def prefill_store_topk_kv(
     """Rank-list store with the reference's argument list.  Deterministic: the slot of a row inside
     its head is its rank order (the reference's atomics make it arbitrary; contract = multiset)."""
     assert new_keys.shape == new_vals.shape
-    if k_cache.dtype == _lib.FP8:
-        raise NotImplementedError("the ranked-list store has no FP8 form: use extract_and_store_top_kv")
+    if k_cache.dtype in (_lib.FP8, _lib.MXFP4):
+        raise NotImplementedError("the ranked-list store has no FP8 / MXFP4 form: use extract_and_store_top_kv")
     N_total, H, D = new_keys.shape
     B = indices_topk.shape[0]
     assert page_table.shape[1] == H

@@ -40,7 +40,8 @@ class Attention(nn.Module):
         # memory_manager.py:82-90); None until then
         for name in ("k_cache", "v_cache", "page_table", "bh_seq_lens", "page_size"):
             setattr(self, name, None)
-        # per-row fp32 scales of an FP8 cache (KVCacheManager.init_cache); None with a 16-bit cache
+        # per-row fp32 scales of an FP8 cache or the e8m0 block-scale bytes of an MXFP4 cache
+        # (KVCacheManager.init_cache); None with a 16-bit cache
         self.k_scale: Optional[torch.Tensor] = None
         self.v_scale: Optional[torch.Tensor] = None
         self.fused_decode: bool = True  # False = the reference's four-call decode sequence
@@ -48,13 +49,17 @@ class Attention(nn.Module):
     # ------------------------------------------------------------------------------------------------ helpers
     def _cache_args(self) -> dict:
         args = dict(page_table=self.page_table, k_cache=self.k_cache, v_cache=self.v_cache, PAGE_SIZE=self.page_size)
-        if self._fp8:
+        if self._fp8 or self._mxfp4:
             args.update(k_scale=self.k_scale, v_scale=self.v_scale)
         return args
 
     @property
     def _fp8(self) -> bool:
         return self.k_cache is not None and self.k_cache.dtype == torch.float8_e4m3fn
+
+    @property
+    def _mxfp4(self) -> bool:
+        return self.k_cache is not None and self.k_cache.dtype == torch.uint8
 
     def _gathered_lengths(self, batch_mapping) -> Optional[torch.Tensor]:
         """[B, HKV] copy of this layer's lengths for the rows of the batch (the reference's `seq_lens`)."""
@@ -80,6 +85,7 @@ class Attention(nn.Module):
         common = dict(self._cache_args(), batch_mapping=batch_mapping, bh_lens=seq_lens,
                       STORE_STREAM=context.STORE_STREAM)
         chunk = getattr(context, "chunk", None)
+        assert chunk is None or not self._mxfp4, "an MXFP4 cache has no chunked prefill"
         compress = context.do_compression and scores is not None and chunk is None
         if compress:
             cc = context.compression_context
@@ -131,10 +137,11 @@ class Attention(nn.Module):
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scores: Optional[torch.Tensor] = None):
         context: Context = get_context()
         batch_mapping = context.batch_mapping
-        if not context.is_prefill and self.fused_decode and self.bh_seq_lens is not None:
+        if not context.is_prefill and self.fused_decode and self.bh_seq_lens is not None and not self._mxfp4:
             # store-then-attend directly on the layer's length table: one C-ABI call instead of
             # index_select + decode_store_kv + attention + index_copy_ (same results, 3 fewer launches); with an
-            # FP8 cache the attention kernel quantises the new row itself
+            # FP8 cache the attention kernel quantises the new row itself.  An MXFP4 cache has no fused step: it takes
+            # the store-then-attend order below.
             assert self.k_cache is not None, "KV Cache must be initialized for decoding"
             return fused_decode_step(q, k, v, self.k_cache, self.v_cache, self.bh_seq_lens, self.page_table,
                                      batch_mapping, int(self.num_kv_heads), self.page_size, self.scale,

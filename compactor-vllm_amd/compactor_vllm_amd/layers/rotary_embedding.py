@@ -82,8 +82,8 @@ def _producer(src, s_n, positions, cos_sin, qw, kw, eps, q_out, k_out, k_pre, HQ
     cs = cos_sin.view(cos_sin.shape[0], -1)
     assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.shape[1] == D
     c = cache
-    if c is not None and c.k_cache.dtype == _lib.FP8:
-        raise NotImplementedError("the producer's fused cache append copies rows: an FP8 cache is written by "
+    if c is not None and c.k_cache.dtype in (_lib.FP8, _lib.MXFP4):
+        raise NotImplementedError("the producer's fused cache append copies rows: an FP8 or MXFP4 cache is written by "
                                   "prefill_store_all_kv")
     st = _lib.lib().cvllm_qkv_rope_producer(
         src.data_ptr(), s_n, pos.data_ptr(), cs.data_ptr(), _lib.ptr(qw), _lib.ptr(kw), float(eps), q_out.data_ptr(),

@@ -411,6 +411,48 @@ int cvllm_prefill_attn_fp8(const void* q, const void* k, const void* v, int64_t 
                            float sm_scale, int dtype, cvllm_stream_t stream, const float* k_scale,
                            const float* v_scale);
 
+/* ---- MXFP4 (OCP e2m1 codes + e8m0 block scales) paged KV cache (csrc/kv_mxfp4.hip) ------------------------------
+ * Codes: k_cache / v_cache [cache_rows, D/2] bytes; byte i of a row holds element 2i in the low nibble and element
+ * 2i+1 in the high nibble; a page is page_size * D/2 contiguous bytes.  Scales: k_scale / v_scale [cache_rows, D/32]
+ * bytes, one per block of 32 consecutive elements, indexed like the codes (a page's scales are page_size * D/32
+ * contiguous bytes).  Paging, page table, lengths and the reserved-row rule are unchanged.  For one block:
+ *     a = max_d |float(x_d)|;  f = the 8-bit exponent field of a as fp32;  s = max(f - 2, 0)   (a == 0: s = 0; s <= 252)
+ *     E = s - 127;  code_d = e2m1(float(x_d) * 2^-E), round to nearest, ties to the even code, saturating at +-6
+ * A nibble's low 3 bits name the magnitude 0, 0.5, 1, 1.5, 2, 3, 4, 6; bit 3 is the sign (unspecified for a zero code).
+ * The value read back is fp32(code) * 2^E: exact in bf16, and in f16 wherever it lies in f16's normal range (blocks
+ * outside it are unspecified on an f16 model, as are NaN / Inf inputs and, in decode, blocks with s = 0 and non-zero
+ * codes).
+ *
+ * The three stores take the argument list of their 16-bit siblings (`dtype` = the SOURCE element type, strides
+ * multiples of 8 elements) plus the two scale arrays; row addressing, slot order, the reserved-row rule and the length
+ * updates are the siblings'.  D in {64, 128}.  No workspace; capture safe where the sibling is.                   */
+int cvllm_store_decode_kv_mxfp4(const void* key, const void* value, int64_t sk_b, int64_t sk_h, int64_t sv_b,
+                                int64_t sv_h, const int32_t* batch_mapping, int32_t* bh_lens,
+                                const int32_t* page_table, void* k_cache, void* v_cache, int B, int HKV, int D,
+                                int page_size, int n_logical_pages_max, int reserved_batch, int dtype,
+                                cvllm_stream_t stream, uint8_t* k_scale, uint8_t* v_scale);
+int cvllm_store_all_kv_mxfp4(const void* new_keys, const void* new_values, int64_t sk_n, int64_t sk_h, int64_t sv_n,
+                             int64_t sv_h, const int32_t* cu_seqlens_k, const int32_t* batch_mapping,
+                             int32_t* bh_lens, const int32_t* page_table, void* k_cache, void* v_cache, int B,
+                             int total_tokens, int HKV, int D, int page_size, int n_logical_pages_max, int dtype,
+                             cvllm_stream_t stream, uint8_t* k_scale, uint8_t* v_scale);
+int cvllm_compact_store_mxfp4(const void* new_keys, const void* new_vals, int64_t sk_n, int64_t sk_h, int64_t sv_n,
+                              int64_t sv_h, const int32_t* kept_idx, const int32_t* new_lens,
+                              const int32_t* cu_seqlens_k, const int32_t* bh_lens0, const int32_t* page_table,
+                              const int32_t* batch_mapping, void* k_cache, void* v_cache, int B, int H, int D,
+                              int max_seqlen, int page_size, int n_logical_pages_max, int dtype,
+                              cvllm_stream_t stream, uint8_t* k_scale, uint8_t* v_scale);
+/* Decode attention over an MXFP4 cache, the contract of cvllm_decode_attn_fp8: q / out [B,HQ,D] in `dtype` (f16 or
+ * bf16); lengths, page table, batch mapping, n_splits and the workspace as cvllm_decode_attn (zero when handed over,
+ * zero again afterwards).  D in {64, 128}, G in {1, 2, 4, 8}, page_size % 32 == 0, any n_logical_pages_max; anything
+ * else CVLLM_ERR_SHAPE, null pointers CVLLM_ERR_ARG, both before any launch.  Splits are merged by the second kernel;
+ * rows with L == 0 produce zeros.  The grid depends on the integer arguments only: capture safe.                  */
+int cvllm_decode_attn_mxfp4(const void* q, const void* k_cache, const void* v_cache, const uint8_t* k_scale,
+                            const uint8_t* v_scale, void* out, const int32_t* seq_lens_bh,
+                            const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
+                            size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
+                            int n_logical_pages_max, float sm_scale, int n_splits, int dtype, cvllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,13 @@ def bench_decode(args):
         scales = [(torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005, torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005)
                   for kc, _ in caches]
         bytes_alg = (2 * D + 8) * B * HKV * L + 4 * B * HQ * D
+    elif args.kv_dtype == "mxfp4":  # random e2m1 codes + e8m0 scales around 2^-2 (csrc/kv_mxfp4.hip); bytes = (D + D/8) * sum L + ...
+        rows = caches[0][0].shape[0]
+        caches = [tuple(torch.randint(0, 256, (rows, D // 2), device=dev, dtype=torch.uint8) for _ in range(2))
+                  for _ in caches]
+        scales = [tuple(torch.randint(123, 128, (rows, D // 32), device=dev, dtype=torch.uint8) for _ in range(2))
+                  for _ in caches]
+        bytes_alg = (D + D // 8) * B * HKV * L + 4 * B * HQ * D
     else:
         scales = [(None, None)] * len(caches)
     from compactor_vllm_amd import _lib
@@ -81,7 +88,7 @@ def bench_decode(args):
                         junk_b.copy_(junk_a)  # do between two layers of a decode step (the GEMVs' weights in between)
                     out = dk.head_sparse_decode_attention(q, kc, vc, lens, pt, bm, HKV, PS, k_scale=ksc, v_scale=vsc)
             us = time_fn(g.replay, iters=50, warmup=max(3, int(40e3 / (25.0 * layers)))) / layers  # ~40 ms of warm replays: settled clocks
-            print(f"decode{' kv=fp8' if fp8 else ''} variant={variant} B={B} L={L} splits={S:3d} layers={layers}: {us:8.2f} us/(stage1+merge)  "
+            print(f"decode{'' if args.kv_dtype == 'model' else ' kv=' + args.kv_dtype} variant={variant} B={B} L={L} splits={S:3d} layers={layers}: {us:8.2f} us/(stage1+merge)  "
                   f"{bytes_alg / us / 1e6:7.3f} TB/s algorithmic", flush=True)
 
 
@@ -291,8 +298,9 @@ if __name__ == "__main__":
     ap.add_argument("--splits", type=int, default=0)
     ap.add_argument("--variant", type=int, default=-1)
     ap.add_argument("--fused-v", type=int, default=0, help="prefill: 1 = V (2 = K and V) as strided views of a fused qkv buffer")
-    ap.add_argument("--kv-dtype", choices=["model", "fp8"], default="model",
-                    help="decode, prefill, scoring --prefix: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales")
+    ap.add_argument("--kv-dtype", choices=["model", "fp8", "mxfp4"], default="model",
+                    help="decode, prefill, scoring --prefix: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales; "
+                         "decode (not --step) only: mxfp4 = e2m1 codes + e8m0 block scales")
     ap.add_argument("--prefix", type=int, default=0, help="prefill, scoring (SnapKV items): cached prefix rows per head in front of the --L appended tokens")
     ap.add_argument("--step", action="store_true", help="decode: whole layer steps (append + attend + lengths), four-call against fused")
     ap.add_argument("--lse", action="store_true", help="decode --step: both legs also return the LSE (the split-KV append rank's step)")
@@ -302,4 +310,6 @@ if __name__ == "__main__":
     ap.add_argument("--with-producer", action="store_true")  # scoring: add the f-2 producer kernel
     ap.add_argument("--only", default="")                # scoring: substring filter on the item name
     a = ap.parse_args()
+    if a.kv_dtype == "mxfp4" and (a.what != "decode" or a.step):
+        ap.error("--kv-dtype mxfp4: decode attention only (no fused step, no prefill or scoring reads)")
     {"decode": bench_decode_step if a.step else bench_decode, "prefill": bench_prefill, "scoring": bench_scoring}[a.what](a)
