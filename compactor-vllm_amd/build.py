@@ -23,9 +23,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # prefill_attn.hip, 4-wave kernel: MFMA results in arch VGPRs (hipcc otherwise selects the ACC-register form for a kernel
 # allowed more than 256 registers and copies every logit back with v_accvgpr_read), and no SLP vectorisation (it pairs
 # the row-sum adds of the two query blocks into v_pk_add_f32 and moves them out of their hand-placed MFMA shadows)
-# prefill_fp8.hip: the 8-wave kernel's tile loop over an FP8 prefix - the flags that loop was tuned under
+# prefill_fp8.hip, prefill_mxfp4.hip: the 8-wave kernel's tile loop over an FP8 / MXFP4 prefix - the flags that loop was
+# tuned under
 FILE_FLAGS = {"prefill_attn.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               "prefill_fp8.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+              "prefill_mxfp4.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               "decode_attn.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
 
 

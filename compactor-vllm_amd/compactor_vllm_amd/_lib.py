@@ -83,6 +83,9 @@ SIGNATURES = {
     "cvllm_compact_store_mxfp4": (_I, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
                                        _I, _I, _P, _P, _P]),
     "cvllm_decode_attn_mxfp4": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
+    "cvllm_compact_cache_inplace_mxfp4": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "cvllm_prefill_attn_mxfp4": (_I, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
+                                      _I, _I, _I, _F, _I, _P, _P, _P]),
     "cvllm_rank_workspace_bytes": (_Z, [_I, _I, _I]),
     "cvllm_rank_indices": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
 }

@@ -2,7 +2,8 @@
 
 Mirror of the reference module `compactor_vllm/attention/sparse_varlen_kernel.py`
 (wrapper :11-197): same name, argument order and assertions; the Triton kernel (:277-519) is
-replaced by `cvllm_prefill_attn` (`cvllm_prefill_attn_fp8` over an FP8 cache).
+replaced by `cvllm_prefill_attn` (`cvllm_prefill_attn_fp8` over an FP8 cache, `cvllm_prefill_attn_mxfp4` over an MXFP4
+cache with a non-empty prefix).
 """
 from __future__ import annotations
 
@@ -38,8 +39,12 @@ def causal_sparse_varlen_with_cache(
     cached prefix lengths BEFORE this step (per kv-head); global_page_table [MAX_BATCHES, HKV, P];
     batch_mapping [B]; cu_seqlens_q [B+1].  With an FP8 cache (k_cache.dtype float8_e4m3fn: e4m3 codes) `k_scale` /
     `v_scale` [CACHE_SIZE] fp32 are the rows' scales and the kernel is `cvllm_prefill_attn_fp8`: a cached element is read
-    back as (fp32(code) * scale) rounded to q.dtype.  `max_seqlen_k_cache` only keys the reference's autotuner
-    (quirk Q10) and is ignored.  Returns [N, HQ, D] contiguous in q.dtype.
+    back as (fp32(code) * scale) rounded to q.dtype.  With an MXFP4 cache (uint8: [CACHE_SIZE, D/2] e2m1 codes) they
+    are [CACHE_SIZE, D/32] uint8 block scales and a cached element is read back as fp32(code) * 2^E
+    (`cvllm_prefill_attn_mxfp4`).  `max_seqlen_k_cache` only keys the reference's autotuner (quirk Q10) and is ignored -
+    except on an MXFP4 cache, where 0 (what the engine passes for a prefill that is neither a chunk nor a prefix hit)
+    means "no prefix": the 16-bit kernel then runs on zeroed lengths and the cache is never dereferenced.  Returns
+    [N, HQ, D] contiguous in q.dtype.
     """
     assert q.ndim == 3, "q should be [N, HQ, D]"
     N, HQ, D = q.shape
@@ -53,11 +58,13 @@ def causal_sparse_varlen_with_cache(
     CACHE_SIZE = k_cache.shape[0]
     assert v_cache.shape[0] == CACHE_SIZE
     mxfp4 = k_cache.dtype == _lib.MXFP4
+    mxfp4_prefix = mxfp4 and int(max_seqlen_k_cache) > 0
     if mxfp4:
-        # No prefill kernel reads 4-bit rows: an MXFP4 cache has no chunked prefill and no prefix reuse, so every prefix is
-        # empty.  The 16-bit kernel runs on zero prefix lengths (a local array: it must never dereference the cache).
         assert k_cache.shape[1] == D // 2 and v_cache.shape[1] == D // 2
-        seq_lens_bh = torch.zeros_like(seq_lens_bh)
+        if not mxfp4_prefix:
+            # No prefix anywhere in the batch (a plain prefill): the faster 16-bit kernel runs on zero prefix lengths (a
+            # local array: it must never dereference the 4-bit cache).
+            seq_lens_bh = torch.zeros_like(seq_lens_bh)
     else:
         assert k_cache.shape[1] == D and v_cache.shape[1] == D
     assert PAGE_SIZE > 0 and CACHE_SIZE % PAGE_SIZE == 0
@@ -80,6 +87,11 @@ def causal_sparse_varlen_with_cache(
         _lib.check_fp8_scales(k_cache, k_scale, v_scale)
         st = _lib.lib().cvllm_prefill_attn_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr())
         _lib.check(st, "cvllm_prefill_attn_fp8")
+    elif mxfp4_prefix:
+        assert v_cache.dtype == _lib.MXFP4
+        _lib.check_mxfp4_scales(k_cache, k_scale, v_scale)
+        st = _lib.lib().cvllm_prefill_attn_mxfp4(*args, k_scale.data_ptr(), v_scale.data_ptr())
+        _lib.check(st, "cvllm_prefill_attn_mxfp4")
     else:
         st = _lib.lib().cvllm_prefill_attn(*args)
         _lib.check(st, "cvllm_prefill_attn")

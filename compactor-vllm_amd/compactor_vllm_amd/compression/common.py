@@ -163,21 +163,29 @@ def compact_cache_inplace(
     k_cache: torch.Tensor,
     v_cache: torch.Tensor,
     PAGE_SIZE: int,
-    k_scale: torch.Tensor | None = None,  # [cache_rows] fp32: with an FP8 (float8_e4m3fn) cache only
+    k_scale: torch.Tensor | None = None,  # FP8 cache: [cache_rows] fp32; MXFP4 (uint8) cache: [cache_rows, D/32] uint8
     v_scale: torch.Tensor | None = None,
 ) -> None:
     """Move the kept rows of every (b, h) down inside the paged cache (last chunk of a chunked prefill): the same final
     cache as `extract_and_store_top_kv` fed with the whole sequence's packed keys / values.  On an FP8 cache a row's
-    codes and its two scales move together (nothing is re-quantised)."""
+    codes and its two scales move together, on an MXFP4 cache its code bytes and its block-scale bytes (nothing is
+    re-quantised)."""
     _lib.require_cuda(kept_idx, new_lens, dst_base, src_base, page_table, batch_mapping, k_cache, v_cache)
     B, H, max_len = kept_idx.shape
+    mxfp4 = k_cache.dtype == _lib.MXFP4
+    D = k_cache.shape[-1] * 2 if mxfp4 else k_cache.shape[-1]
     args = (kept_idx.data_ptr(), new_lens.data_ptr(), _lib.i32(dst_base).data_ptr(), _lib.i32(src_base).data_ptr(),
             page_table.data_ptr(), _lib.i32(batch_mapping).data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), B, H,
-            k_cache.shape[-1], int(max_len), int(PAGE_SIZE), page_table.shape[-1])
+            D, int(max_len), int(PAGE_SIZE), page_table.shape[-1])
     if k_cache.dtype == _lib.FP8:
         _lib.check_fp8_scales(k_cache, k_scale, v_scale)
         st = _lib.lib().cvllm_compact_cache_inplace_fp8(*args, _lib.stream(), k_scale.data_ptr(), v_scale.data_ptr())
         _lib.check(st, "cvllm_compact_cache_inplace_fp8")
+    elif mxfp4:
+        _lib.check_mxfp4_scales(k_cache, k_scale, v_scale)
+        assert v_cache.shape == k_cache.shape
+        st = _lib.lib().cvllm_compact_cache_inplace_mxfp4(*args, _lib.stream(), k_scale.data_ptr(), v_scale.data_ptr())
+        _lib.check(st, "cvllm_compact_cache_inplace_mxfp4")
     else:
         st = _lib.lib().cvllm_compact_cache_inplace(*args, _lib.dtype_code(k_cache.dtype), _lib.stream())
         _lib.check(st, "cvllm_compact_cache_inplace")

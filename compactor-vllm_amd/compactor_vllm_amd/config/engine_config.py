@@ -33,11 +33,15 @@ class LLMConfig:
     attention_backend: AttentionBackend = AttentionBackend.COMPACTOR_TRITON
     show_progress_bar: bool = True
     # "auto" = the model dtype; "fp8_e4m3" = e4m3 codes + one fp32 scale per cache row; "mxfp4" = OCP e2m1 codes + one
-    # e8m0 scale per 32 elements (no chunked prefill, no prefix reuse)
+    # e8m0 scale per 32 elements
     kv_cache_dtype: str = "auto"
     # FP8 cache only: prefill attention reads the FP8 prefix (cvllm_prefill_attn_fp8), which turns chunked prefill and
     # prefix reuse on.  Opt-in for now; without it an FP8 cache refuses both, as before.
     fp8_prefix_reads: bool = False
+    # MXFP4 cache only, the same switch: prefill attention reads the 4-bit prefix (cvllm_prefill_attn_mxfp4).  Without it an
+    # MXFP4 cache has no chunked prefill and no prefix reuse.  SnapKV scoring does not read 4-bit rows: with it a chunked
+    # prompt or a prefix hit raises NotImplementedError.
+    mxfp4_prefix_reads: bool = False
 
     def __post_init__(self):
         if self.kv_cache_dtype not in ("auto", "fp8_e4m3", "mxfp4"):

@@ -52,9 +52,11 @@ class KVCacheManager:
         if self.fp8 and not self.fp8_prefix_reads:
             self.chunked_prefill = False  # FP8 prefix reads in prefill attention are opt-in (LLMConfig.fp8_prefix_reads)
         self.mxfp4 = getattr(config, "kv_cache_dtype", "auto") == "mxfp4"
-        if self.mxfp4:  # e2m1 codes + e8m0 block scales; no prefill kernel reads them: no chunked prefill, no prefix reuse
+        self.mxfp4_prefix_reads = self.mxfp4 and bool(getattr(config, "mxfp4_prefix_reads", False))
+        if self.mxfp4:  # e2m1 codes + e8m0 block scales
             self.cache_dtype = torch.uint8
-            self.chunked_prefill = False
+            if not self.mxfp4_prefix_reads:  # MXFP4 prefix reads in prefill attention are opt-in, as FP8's
+                self.chunked_prefill = False
 
     # ---- sizing ------------------------------------------------------------------------------------------------
     def bytes_per_page_all_layers(self) -> int:

@@ -113,6 +113,12 @@ class ModelRunner:
         `state` holds their scoring stash (prefix reuse); `finish=False`: no chunk is the last one (a prefix being
         registered: nothing is compressed, the state is the caller's to keep)."""
         assert a.B == 1
+        from ..compression.compression_config import CompressionMethod
+
+        if self.kv_manager.mxfp4 and a.do_compression and a.compression_method == CompressionMethod.SNAPKV:
+            raise NotImplementedError("SnapKV with a chunked prompt or a prefix hit on an MXFP4 cache: its scoring reads "
+                                      "the cached keys through cvllm_snapkv_scores_paged, which does not read 4-bit rows "
+                                      "(unchunked SnapKV prefills work)")
         total = int(a.context_lens[0])
         cuts = [start + c for c in chunk_boundaries(total - start, self.max_batched_tokens)]
         if state is None:
@@ -159,9 +165,9 @@ class ModelRunner:
         if self.kv_manager.fp8 and not self.kv_manager.fp8_prefix_reads:
             raise NotImplementedError("prefix reuse on an FP8 cache (kv_cache_dtype='fp8_e4m3') needs prefill attention "
                                       "over FP8 rows: set LLMConfig.fp8_prefix_reads=True")
-        if self.kv_manager.mxfp4:
+        if self.kv_manager.mxfp4 and not self.kv_manager.mxfp4_prefix_reads:
             raise NotImplementedError("prefix reuse on an MXFP4 cache (kv_cache_dtype='mxfp4') needs prefill attention "
-                                      "over 4-bit rows, which does not exist")
+                                      "over 4-bit rows: set LLMConfig.mxfp4_prefix_reads=True")
         params = batch_compression_params if batch_compression_params is not None else BatchCompressionParams()
         method, chunk = self._scoring_key(params)
         P = (len(token_ids) // PREFIX_ALIGN) * PREFIX_ALIGN
@@ -206,8 +212,8 @@ class ModelRunner:
 
     @torch.inference_mode()
     def run_prefill_with_prefix(self, a: PrefillBatchArguments, batch_mapping: torch.Tensor, entry: PrefixEntry) -> torch.Tensor:
-        """The request's row receives a copy of the prefix's K/V pages (every layer, every head; on an FP8 cache the codes
-        and the scales), its lengths start at P, and the suffix runs as the remaining chunk(s) of a chunked prefill whose scoring state starts from the
+        """The request's row receives a copy of the prefix's K/V pages (every layer, every head; on an FP8 or MXFP4 cache
+        the codes and the scales), its lengths start at P, and the suffix runs as the remaining chunk(s) of a chunked prefill whose scoring state starts from the
         prefix's stash."""
         cache = self.kv_manager.paged_cache
         P, PS = entry.length, cache.page_size
@@ -216,13 +222,15 @@ class ModelRunner:
         L, H = cache.num_layers, cache.H_kv
         src = cache.page_table[:, entry.row, :, :npg].long()  # [L, H, npg] physical pages
         dst = cache.page_table[:, row, :, :npg].long()
-        # bytes are copied (an FP8 cache as uint8), and an FP8 cache's scale pages go along with its code pages
+        # bytes are copied (an FP8 cache as uint8), and a quantised cache's scale pages go along with its code pages; the
+        # row width is whatever the cache holds (head_dim, or head_dim / 2 bytes of MXFP4 codes), and a scale row is one
+        # fp32 (FP8) or head_dim / 32 bytes (MXFP4)
         raw = cache.kv_cache.view(torch.uint8) if cache.kv_scale is not None else cache.kv_cache
-        kv = raw.view(2, L, cache.n_pages, PS, cache.head_dim)
+        kv = raw.view(2, L, cache.n_pages, PS, raw.shape[-1])
         li = torch.arange(L, device=src.device)[:, None, None].expand_as(src)
         kv[:, li, dst] = kv[:, li, src]
         if cache.kv_scale is not None:
-            sc = cache.kv_scale.view(2, L, cache.n_pages, PS)
+            sc = cache.kv_scale.view(2, L, cache.n_pages, PS, -1)
             sc[:, li, dst] = sc[:, li, src]
         cache.bh_seq_lens[:, row] = P
         total = int(a.context_lens[0])

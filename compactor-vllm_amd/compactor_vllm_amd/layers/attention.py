@@ -85,7 +85,6 @@ class Attention(nn.Module):
         common = dict(self._cache_args(), batch_mapping=batch_mapping, bh_lens=seq_lens,
                       STORE_STREAM=context.STORE_STREAM)
         chunk = getattr(context, "chunk", None)
-        assert chunk is None or not self._mxfp4, "an MXFP4 cache has no chunked prefill"
         compress = context.do_compression and scores is not None and chunk is None
         if compress:
             cc = context.compression_context

@@ -12,7 +12,8 @@
 // Stores: a row is D/16 lanes, each holding 16 source elements; a block is a pair of adjacent lanes, its maximum one DPP
 // exchange inside the pair.  A lane packs its 16 codes into 8 bytes in registers and writes them with one 8 B store; the
 // even lane of a pair writes the block's scale byte.  Addressing, slot order, the RESERVED-row rule and the length
-// updates are those of store_kv.hip / kv_fp8.hip.
+// updates are those of store_kv.hip / kv_fp8.hip.  The in-place compaction behind a chunked prefill moves code and scale
+// bytes as they are (compact_inplace_mxfp4_kernel); the prefill kernel that reads them is prefill_mxfp4.hip.
 //
 // Decode attention (decode_mxfp4_kernel): the streaming skeleton of decode_fp8_kernel - one workgroup of 4 waves per
 // (b, kv-head, split), wave-private LDS rings filled by LDS-DMA, a counted vmcnt, no barrier in the loop, page ids
@@ -175,6 +176,79 @@ __global__ __launch_bounds__(256) void compact_store_mxfp4_kernel(
     const size_t prow = (size_t)pt[pos / PS] * PS + pos % PS;
     mx_row_store<T, D>(key + (size_t)n * sk_n + h * sk_h, kc + prow * (D / 2), ksc + prow * (D / 32), dl);
     mx_row_store<T, D>(value + (size_t)n * sv_n + h * sv_h, vc + prow * (D / 2), vsc + prow * (D / 32), dl);
+  }
+}
+
+// ---- compaction IN PLACE (last chunk of a chunked prefill on an MXFP4 cache) ----------------------------------------------
+// Sibling of compact_inplace_kernel (store_kv.hip) and compact_inplace_fp8_kernel: the kept rows of every (b,h) move down
+// to slots dst_base.. in token order.  The bits move as they are - D/2 code bytes and D/32 scale bytes, for K and for V,
+// nothing is re-quantised - so the result is what compact_store_mxfp4_kernel writes from the packed 16-bit rows, byte for
+// byte.  The no-overlap argument is that kernel's: with an ascending kept list slot j receives the row of token t_j >= j,
+// tile i writes slots below dst_base + TILE (i + 1) and every source of a later tile lies at or above
+// src_base + TILE (i + 1); inside a tile a barrier separates all loads from all stores, and the next tile's loads are
+// issued before this tile's stores.
+// A row is D/32 lanes; lane dl carries 16 B of codes = 32 elements = scale block dl, and that block's scale byte.
+template <int D>
+__global__ __launch_bounds__(256) void compact_inplace_mxfp4_kernel(
+    const int* __restrict__ kept_idx, const int* __restrict__ new_lens, const int* __restrict__ dst_base,
+    const int* __restrict__ src_base, const int* __restrict__ page_table, const int* __restrict__ bmap,
+    uint8_t* __restrict__ kc, uint8_t* __restrict__ vc, uint8_t* __restrict__ ksc, uint8_t* __restrict__ vsc, int H,
+    int max_seqlen, int PS, int NLP) {
+  constexpr int RB = D / 2;           // code bytes per row
+  constexpr int LPR = D / 32;         // lanes per row = scale bytes per row
+  constexpr int RPP = 256 / LPR;      // rows per pass of the workgroup
+  constexpr int TILE = 128;           // rows per tile, as the siblings
+  constexpr int PASSES = TILE / RPP;  // rows per thread and tile
+  const int bh = blockIdx.x;
+  const int b = bh / H, h = bh % H;
+  const int d0 = dst_base[bh], s0 = src_base[bh];
+  const int cnt = new_lens[bh] - d0;
+  const int tok_max = NLP * PS - 1 - s0;  // last row the page table can address
+  const int dl = threadIdx.x % LPR, rl = threadIdx.x / LPR;
+  const int* list = kept_idx + (size_t)bh * max_seqlen;
+  const int* pt = page_table + ((size_t)bmap[b] * H + h) * NLP;
+  auto row_of = [&](int pos) { return (size_t)pt[pos / PS] * PS + pos % PS; };
+  struct Rows {
+    uint4 k[PASSES], v[PASSES];
+    uint8_t ks[PASSES], vs[PASSES];
+  };
+  Rows buf[2];
+  auto load_tile = [&](int t0, Rows& x) {
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      const int j = t0 + p * RPP + rl;
+      if (j < cnt) {
+        const size_t a = row_of(s0 + max(0, min(list[j], tok_max)));  // clamped: see compact_store_kernel
+        x.k[p] = *reinterpret_cast<const uint4*>(kc + a * RB + dl * 16);
+        x.v[p] = *reinterpret_cast<const uint4*>(vc + a * RB + dl * 16);
+        x.ks[p] = ksc[a * LPR + dl];
+        x.vs[p] = vsc[a * LPR + dl];
+      }
+    }
+  };
+  auto store_tile = [&](int t0, const Rows& x) {
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      const int j = t0 + p * RPP + rl;
+      if (j < cnt) {
+        const size_t a = row_of(d0 + j);
+        *reinterpret_cast<uint4*>(kc + a * RB + dl * 16) = x.k[p];
+        *reinterpret_cast<uint4*>(vc + a * RB + dl * 16) = x.v[p];
+        ksc[a * LPR + dl] = x.ks[p];
+        vsc[a * LPR + dl] = x.vs[p];
+      }
+    }
+  };
+  if (cnt <= 0) return;
+  load_tile(0, buf[0]);
+  for (int t0 = 0; t0 < cnt; t0 += 2 * TILE) {
+    if (t0 + TILE < cnt) load_tile(t0 + TILE, buf[1]);
+    __syncthreads();  // every row of tile t0 is in registers (the barrier also drains each wave's loads)
+    store_tile(t0, buf[0]);
+    if (t0 + TILE >= cnt) break;
+    if (t0 + 2 * TILE < cnt) load_tile(t0 + 2 * TILE, buf[0]);
+    __syncthreads();
+    store_tile(t0 + TILE, buf[1]);
   }
 }
 
@@ -681,6 +755,28 @@ extern "C" int cvllm_compact_store_mxfp4(const void* new_keys, const void* new_v
                        cu_seqlens_k, bh_lens0, page_table, batch_mapping, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale,
                        v_scale, H, max_seqlen, page_size, n_logical_pages_max, tiles);
   });
+  return check_launch();
+}
+
+extern "C" int cvllm_compact_cache_inplace_mxfp4(const int32_t* kept_idx, const int32_t* new_lens,
+                                                 const int32_t* dst_base, const int32_t* src_base,
+                                                 const int32_t* page_table, const int32_t* batch_mapping,
+                                                 void* k_cache, void* v_cache, int B, int H, int D, int max_seqlen,
+                                                 int page_size, int n_logical_pages_max, cvllm_stream_t stream,
+                                                 uint8_t* k_scale, uint8_t* v_scale) {
+  if (!kept_idx || !new_lens || !dst_base || !src_base || !page_table || !batch_mapping || !k_cache || !v_cache ||
+      !k_scale || !v_scale)
+    return CVLLM_ERR_ARG;
+  if (B <= 0 || H <= 0 || max_seqlen <= 0 || page_size <= 0 || n_logical_pages_max <= 0) return CVLLM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+#define CI_CALL(D_)                                                                                                   \
+  hipLaunchKernelGGL((compact_inplace_mxfp4_kernel<D_>), dim3(B* H), dim3(256), 0, st, kept_idx, new_lens, dst_base,  \
+                     src_base, page_table, batch_mapping, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, H,  \
+                     max_seqlen, page_size, n_logical_pages_max)
+  if (D == 64) CI_CALL(64);
+  else if (D == 128) CI_CALL(128);
+  else return CVLLM_ERR_SHAPE;
+#undef CI_CALL
   return check_launch();
 }
 

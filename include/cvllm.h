@@ -452,6 +452,29 @@ int cvllm_decode_attn_mxfp4(const void* q, const void* k_cache, const void* v_ca
                             const int32_t* page_table, const int32_t* batch_mapping, void* workspace,
                             size_t workspace_bytes, int B, int HQ, int HKV, int D, int page_size,
                             int n_logical_pages_max, float sm_scale, int n_splits, int dtype, cvllm_stream_t stream);
+/* MXFP4 cache, in-place compaction: cvllm_compact_cache_inplace on e2m1 codes.  A kept row's D/2 code bytes and D/32
+ * scale bytes move together, for K and for V, and nothing is re-quantised: the same bytes as cvllm_compact_store_mxfp4
+ * fed with the packed 16-bit rows.  D in {64, 128}, anything else CVLLM_ERR_SHAPE; null pointers CVLLM_ERR_ARG. */
+int cvllm_compact_cache_inplace_mxfp4(const int32_t* kept_idx, const int32_t* new_lens,
+                                      const int32_t* dst_base, const int32_t* src_base,
+                                      const int32_t* page_table, const int32_t* batch_mapping,
+                                      void* k_cache, void* v_cache, int B, int H, int D, int max_seqlen,
+                                      int page_size, int n_logical_pages_max, cvllm_stream_t stream,
+                                      uint8_t* k_scale, uint8_t* v_scale);
+/* MXFP4 cache, prefill attention: cvllm_prefill_attn over [MXFP4 cached prefix || 16-bit appended block]
+ * (csrc/prefill_mxfp4.hip).  The argument list is cvllm_prefill_attn_fp8's with byte scales: k_cache / v_cache
+ * [cache_rows, D/2] codes, k_scale / v_scale [cache_rows, D/32]; q, k, v, out stay f16 / bf16.  A cached element is read
+ * back as fp32(code) * 2^E, with no further rounding (exact in bf16; in f16 as stated above).  A cache row at or beyond a
+ * head's length is never read.  D in {64, 128}, HQ / HKV in {1, 2, 4, 8}, any page size, any n_logical_pages_max, f16 or
+ * bf16; anything else CVLLM_ERR_SHAPE, null pointers CVLLM_ERR_ARG, both before any launch. */
+int cvllm_prefill_attn_mxfp4(const void* q, const void* k, const void* v, int64_t sq_n, int64_t sk_n,
+                             int64_t sk_h, int64_t sv_n, int64_t sv_h, const void* k_cache,
+                             const void* v_cache, void* out, const int32_t* seq_lens_bh,
+                             const int32_t* page_table, const int32_t* batch_mapping,
+                             const int32_t* cu_seqlens_q, int B, int total_tokens, int max_seqlen_q,
+                             int HQ, int HKV, int D, int page_size, int n_logical_pages_max,
+                             float sm_scale, int dtype, cvllm_stream_t stream, const uint8_t* k_scale,
+                             const uint8_t* v_scale);
 
 #ifdef __cplusplus
 }

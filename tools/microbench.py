@@ -181,6 +181,11 @@ def bench_prefill(args):
             kc, vc = kc.to(torch.float8_e4m3fn), vc.to(torch.float8_e4m3fn)
             scales = dict(k_scale=torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005,
                           v_scale=torch.rand(kc.shape[0], device=dev) * 0.01 + 0.005)
+        elif args.kv_dtype == "mxfp4":  # random e2m1 codes + e8m0 scales around 2^-2: cvllm_prefill_attn_mxfp4 when Pc > 0
+            rows = kc.shape[0]
+            kc, vc = (torch.randint(0, 256, (rows, D // 2), device=dev, dtype=torch.uint8) for _ in range(2))
+            scales = {n: torch.randint(123, 128, (rows, D // 32), device=dev, dtype=torch.uint8)
+                      for n in ("k_scale", "v_scale")}
         cu = torch.arange(0, B + 1, dtype=torch.int32, device=dev) * L
         fn = lambda: causal_sparse_varlen_with_cache(q, k, v, kc, vc, lens, pt, bm, cu, L, Pc, HKV, PS, **scales)
         # warm until ~40 ms of this kernel have run: with 2 warm launches a 16 K kernel (2 ms) was still timed on a ramping
@@ -188,7 +193,7 @@ def bench_prefill(args):
         warm = max(2, min(40, int(40e-3 / (4e-9 * 2 * L * (L / 2 + Pc) * B / 1e3 + 1e-4))))
         us = time_fn(fn, iters=max(5, warm // 2), warmup=warm)
         flops = 4 * D * HQ * B * (L * Pc + L * (L + 1) / 2)
-        print(f"prefill{' kv=fp8' if scales else ''} B={B} L={L} prefix={Pc}: {us / 1e3:9.3f} ms  "
+        print(f"prefill{' kv=' + args.kv_dtype if scales else ''} B={B} L={L} prefix={Pc}: {us / 1e3:9.3f} ms  "
               f"{flops / us / 1e6:8.1f} TFLOP/s (causal flops)", flush=True)
 
 
@@ -300,7 +305,7 @@ if __name__ == "__main__":
     ap.add_argument("--fused-v", type=int, default=0, help="prefill: 1 = V (2 = K and V) as strided views of a fused qkv buffer")
     ap.add_argument("--kv-dtype", choices=["model", "fp8", "mxfp4"], default="model",
                     help="decode, prefill, scoring --prefix: the cache's element type - the model dtype (bf16) or FP8 e4m3 codes + per-row scales; "
-                         "decode (not --step) only: mxfp4 = e2m1 codes + e8m0 block scales")
+                         "decode (not --step) and prefill only: mxfp4 = e2m1 codes + e8m0 block scales")
     ap.add_argument("--prefix", type=int, default=0, help="prefill, scoring (SnapKV items): cached prefix rows per head in front of the --L appended tokens")
     ap.add_argument("--step", action="store_true", help="decode: whole layer steps (append + attend + lengths), four-call against fused")
     ap.add_argument("--lse", action="store_true", help="decode --step: both legs also return the LSE (the split-KV append rank's step)")
@@ -310,6 +315,6 @@ if __name__ == "__main__":
     ap.add_argument("--with-producer", action="store_true")  # scoring: add the f-2 producer kernel
     ap.add_argument("--only", default="")                # scoring: substring filter on the item name
     a = ap.parse_args()
-    if a.kv_dtype == "mxfp4" and (a.what != "decode" or a.step):
-        ap.error("--kv-dtype mxfp4: decode attention only (no fused step, no prefill or scoring reads)")
+    if a.kv_dtype == "mxfp4" and (a.what == "scoring" or a.step):
+        ap.error("--kv-dtype mxfp4: decode and prefill attention only (no fused step, no scoring reads)")
     {"decode": bench_decode_step if a.step else bench_decode, "prefill": bench_prefill, "scoring": bench_scoring}[a.what](a)
